@@ -7,13 +7,20 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with
+Prints ONE JSON line on rank 0: metric, value (volumes/s), unit, higher_is_better, dtype, ms_per_step (the time of one
+timed step) and the run's config.  A plain run does only that: set up, warm up, time --steps steps.  With --full the line
+also holds
   roofline     : matrix-core roofline of the dominant kernel (all launches of that conv kernel in a step),
-                 algorithmic FLOPs / HIP-event time measured live on the launch stream
+                 algorithmic FLOPs / HIP-event time measured live on the launch stream (--no-roofline skips it)
   cpu_baseline : the oracle (torch-CPU restatement of the reference, oracle/) timed on this box's
                  host cores on one 1x1x128^3 volume (rank 0, N=1 only): one warm-up pass + two timed passes, median
-  secondary    : (default N=1 run only) configs[2] MedFormer, configs[4] SwinUNETR and configs[3] ResUNet + on-device
+                 (--no-cpu-baseline skips it)
+  secondary    : (N=1 headline run only) configs[2] MedFormer, configs[4] SwinUNETR and configs[3] ResUNet + on-device
                  augmentation timed in the same process for 10 replayed steps each (--secondary 0 skips them)
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, a fixed seeded sample of
+the large tensors): the loss, the logits, the updated parameters and their gradients.  The inputs, the initial weights and
+the sample positions depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -51,8 +58,13 @@ def parse():
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--base", type=int, default=32)
     ap.add_argument("--classes", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the dominant-kernel roofline, the secondary "
+                         "models and the CPU baseline (each of them can still be switched off on its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the dominant-kernel roofline")
     ap.add_argument("--graph", type=int, default=1,
                     help="1: replay the whole step (incl. the RCCL gradient all-reduce for N > 1) from one hipGraph, "
                          "captured after warm-up; falls back to eager launches if the capture fails")
@@ -66,13 +78,17 @@ def parse():
     ap.add_argument("--model", default="resunet", choices=["resunet", "medformer", "swin_unetr"],
                     help="resunet = BASELINE configs[1] (the headline); medformer = configs[2] (AMOS yaml, aux loss); swin_unetr = configs[4] (4-modality input, feature 48, 4 classes)")
     ap.add_argument("--secondary", type=int, default=1,
-                    help="1 (default; N=1 headline run only): after the headline timing, also time MedFormer (configs[2]), SwinUNETR "
+                    help="1 (default; --full, N=1 headline run only): after the headline timing, also time MedFormer (configs[2]), SwinUNETR "
                          "(configs[4]) and --aug 1 (configs[3]) for --secondary-steps replayed steps each and report them in `secondary`")
     ap.add_argument("--secondary-steps", type=int, default=10)
     ap.add_argument("--aug", type=int, default=0,
                     help="1: draw each step's volume with the on-device augmentation pipeline (configs[3]): affine "
                          "scale/rotate + centre crop from a (size+40)^3 source, then the intensity ops")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline alone
+        args.no_cpu_baseline, args.no_roofline, args.secondary = True, True, 0
+    return args
 
 
 def synthetic(batch, classes, size, device, seed):
@@ -298,6 +314,9 @@ def time_model(args, dev, rank, world, on_hang=None):
     def draw():
         return feeder.next()
 
+    last = {}        # --dump-outputs: the logits of the latest step (under replay: the graph's own output buffer), detached:
+                     # a reference to the step's autograd graph would keep its AccumulateGrad nodes alive into the capture
+
     def step():
         opt.zero_grad(set_to_none=True)
         if args.aug:
@@ -305,6 +324,8 @@ def time_model(args, dev, rank, world, on_hang=None):
             x.copy_(xs)
             lab.copy_(ls)
         out = net(x)
+        if args.dump_outputs:
+            last["out"] = [o.detach() for o in out] if isinstance(out, (list, tuple)) else out.detach()
         ls = lab
         if isinstance(out, (list, tuple)):      # deep supervision, train.py:207-210 (aux_weight [0.5, 0.5])
             loss = sum(0.5 * crit(o, ls) for o in out)
@@ -360,6 +381,12 @@ def time_model(args, dev, rank, world, on_hang=None):
                     for _ in range(2):
                         step()
                     opt.zero_grad(set_to_none=True)
+                    if ddp is not None and dist.get_backend() == "nccl":
+                        # the warm-up collectives must have left the process group's watchdog queue before the capture
+                        # opens: a watchdog that queries their HIP events while the capture is open gets an error back
+                        # and aborts the process (a race, so an intermittent failure)
+                        torch.cuda.synchronize()
+                        dist.distributed_c10d._get_default_group()._wait_for_pending_works()
                     # the RCCL collectives of the gradient exchange are captured with the kernels (N > 1): every rank
                     # captures and replays the same sequence
                     args.aug = 0                        # the captured step reads the static buffers x / lab
@@ -411,7 +438,8 @@ def time_model(args, dev, rank, world, on_hang=None):
         watchdog.cancel()
     ms = dt / args.steps * 1e3
     loss_val = float(loss.item())
-    res = dict(facts, ms=ms, dt=dt, graph=bool(use_graph), loss=loss_val, eager_step=eager_step, ddp=ddp, keep=(net, opt, crit, x, lab))
+    res = dict(facts, ms=ms, dt=dt, graph=bool(use_graph), loss=loss_val, eager_step=eager_step, ddp=ddp, keep=(net, opt, crit, x, lab),
+               net=net, out=last.pop("out", None))
     if eager_res is not None:
         res["eager_ms"] = eager_res["ms"]
     if dist.is_initialized() and world > 1:
@@ -491,6 +519,41 @@ def _recorded_traffic(model, size):
 ALG_BYTES_STEP = {"resunet": ALG_BYTES_BF16, "medformer": 15.9e9, "swin_unetr": 14.22e9}
 
 
+DUMP_SAMPLE = {"logits": 1 << 21, "params": 1 << 22, "grads": 1 << 22}     # elements kept of each large output (<= 64 MB in all)
+
+
+def _sample(t, k):
+    """all of `t` (flattened, float32) when it has at most k elements, else k positions drawn with a fixed seed from its size
+    alone (sorted; the same positions in every run and every build)"""
+    t = t.detach().reshape(-1).float()
+    if t.numel() > k:
+        idx = torch.randint(0, t.numel(), (k,), generator=torch.Generator().manual_seed(2023)).sort().values
+        t = t[idx.to(t.device)]
+    return t.cpu().numpy()
+
+
+def dump_outputs(path, r):
+    """the outputs of the last timed step as <path>/<name>.npy: the loss (float64), the logits (every output of a deep-supervised
+    model), the updated parameters and their gradients (all tensors flattened and concatenated in named_parameters order,
+    sampled), and per parameter tensor [sum, sum of squares] of both (float64, every element)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": np.array([r["loss"]], dtype=np.float64)}
+    outs = r["out"]
+    if outs is not None:
+        outs = list(outs) if isinstance(outs, (list, tuple)) else [outs]
+        for i, o in enumerate(outs):
+            arrays["logits" if len(outs) == 1 else f"logits_{i}"] = _sample(o, DUMP_SAMPLE["logits"])
+    params = [p for _, p in r["net"].named_parameters()]
+    grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
+    for name, ts in (("params", params), ("grads", grads)):
+        arrays[name] = _sample(torch.cat([t.detach().reshape(-1).float() for t in ts]), DUMP_SAMPLE[name])
+        arrays[name[:-1] + "_stats"] = torch.stack([torch.stack([t.detach().double().sum(), t.detach().double().square().sum()])
+                                                    for t in ts]).cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def secondary(args, dev):
     """BASELINE.json configs[2] (MedFormer), configs[4] (SwinUNETR, per-GPU part) and configs[3] (ResUNet with the on-device
     augmentation pipeline, per-GPU part) timed in THIS process after the headline: `--secondary-steps` replayed steps each
@@ -503,7 +566,7 @@ def secondary(args, dev):
                                  ("swin_unetr", "swin_unetr", 0, FWD_FLOPS_128_SWIN),
                                  ("resunet_aug", "resunet", 1, FWD_FLOPS_128)):
         a = _ap.Namespace(**vars(args))
-        a.model, a.aug, a.steps, a.warmup = model, aug, args.secondary_steps, 3
+        a.model, a.aug, a.steps, a.warmup, a.dump_outputs = model, aug, args.secondary_steps, 3, None
         _release(dev)
         t0 = time.perf_counter()
         try:
@@ -594,6 +657,10 @@ def main():
         print(json.dumps(build_out(r)), flush=True)
 
     box = [time_model(args, dev, rank, world, on_hang=on_hang)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, box[0])
+    for k in ("net", "out"):
+        box[0].pop(k)
     _finish(args, build_out(box[0]), box, rank, world, dev)
 
 

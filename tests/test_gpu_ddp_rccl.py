@@ -65,7 +65,7 @@ def test_two_rank_control_flow_of_bench_on_one_gpu():
     vehicle, never a bench line): self-spawn through torch.distributed.run, rank-0 broadcast, bucketed exchange from the backward hooks,
     the eager timing taken first, a graph attempt that gloo refuses on every rank -> the all-ranks agreement falls back to eager
     launches, the roofline's eager steps run on EVERY rank (they hold collectives), one JSON line."""
-    d, err = _bench2({})
+    d, err = _bench2({}, "--full")
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2" and d["config"]["global_batch"] == 2
     assert d["config"]["graph"] is False and "eager_ms_per_step" in d["config"], (d["config"], err[-1500:])
     assert d["value"] == pytest.approx(2.0 / (d["ms_per_step"] * 1e-3))

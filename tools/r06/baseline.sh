@@ -13,4 +13,4 @@ for m in swin_unetr medformer; do
   python $R/tools/rocpd_summary.py /tmp/pf_$m/p_results.db 7 > $O/r06_a_${m}_kernels.txt 2>&1
   for k in k_conv_igemm k_conv_wgrad k_wgrad_reduce k_resnorm k_conv3_rw k_wgrad_r32; do python $R/tools/rocpd_by_grid.py /tmp/pf_$m/p_results.db $k; done > $O/r06_a_${m}_by_grid.txt 2>&1
 done
-cd $R; python bench.py --no-cpu-baseline --secondary 1 > $O/r06_a_bench.json 2> $O/r06_a_bench.err
+cd $R; python bench.py --full --no-cpu-baseline --secondary 1 > $O/r06_a_bench.json 2> $O/r06_a_bench.err

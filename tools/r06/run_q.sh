@@ -17,7 +17,7 @@ for v in 0 1; do
   CBIM_CONV_RW48_HALF=$v python bench.py --model swin_unetr --steps 20 --warmup 5 --no-roofline --no-cpu-baseline --secondary 0 2>/dev/null | tail -1 | python -c "import sys, json; d = json.loads(sys.stdin.read()); print('   swin_unetr ms/step', round(d['ms_per_step'], 3))"
 done 2>&1 | tee $O/${T}_half_ab.txt
 for rep in 1 2; do
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --secondary 0 2>/dev/null | tail -1 | python -c "import sys, json; d = json.loads(sys.stdin.read()); print('round-6 conv_rw.hip: resunet ms/step', round(d['ms_per_step'], 3), 'k_conv3_rw avg launch us', round(d['roofline']['avg_launch_ms'] * 1e3, 2))"
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --secondary 0 2>/dev/null | tail -1 | python -c "import sys, json; d = json.loads(sys.stdin.read()); print('round-6 conv_rw.hip: resunet ms/step', round(d['ms_per_step'], 3), 'k_conv3_rw avg launch us', round(d['roofline']['avg_launch_ms'] * 1e3, 2))"
 done | tee $O/${T}_headline_ab.txt
 cp cbim-medical-image-segmentation_amd/csrc/conv_rw.hip /tmp/conv_rw_r06.hip
 python - <<'PY'
@@ -33,5 +33,5 @@ open("cbim-medical-image-segmentation_amd/csrc/conv_rw.hip", "w").write(s)
 PY
 make -C cbim-medical-image-segmentation_amd/csrc 2>&1 | tail -1
 for rep in 1 2; do
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --secondary 0 2>/dev/null | tail -1 | python -c "import sys, json; d = json.loads(sys.stdin.read()); print('round-5 conv_rw.hip: resunet ms/step', round(d['ms_per_step'], 3), 'k_conv3_rw avg launch us', round(d['roofline']['avg_launch_ms'] * 1e3, 2))"
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --secondary 0 2>/dev/null | tail -1 | python -c "import sys, json; d = json.loads(sys.stdin.read()); print('round-5 conv_rw.hip: resunet ms/step', round(d['ms_per_step'], 3), 'k_conv3_rw avg launch us', round(d['roofline']['avg_launch_ms'] * 1e3, 2))"
 done | tee -a $O/${T}_headline_ab.txt

@@ -10,10 +10,10 @@ if [ "$2" = "suite" ]; then
   tail -4 $O/${T}_gputest.log
   python -c "import __graft_entry__ as g; g.smoke()" > $O/${T}_smoke.log 2>&1; tail -3 $O/${T}_smoke.log
 fi
-python $R/bench.py > $O/${T}_resunet_bench.json 2> $O/${T}_resunet_bench.err
-python $R/bench.py --model medformer --cpu-size 64 > $O/${T}_medformer_bench.json 2> $O/${T}_medformer_bench.err
-python $R/bench.py --model swin_unetr --cpu-size 64 > $O/${T}_swin_bench.json 2> $O/${T}_swin_bench.err
-python $R/bench.py --aug 1 --no-cpu-baseline > $O/${T}_resunet_aug_bench.json 2> $O/${T}_resunet_aug_bench.err
+python $R/bench.py --full > $O/${T}_resunet_bench.json 2> $O/${T}_resunet_bench.err
+python $R/bench.py --full --model medformer --cpu-size 64 > $O/${T}_medformer_bench.json 2> $O/${T}_medformer_bench.err
+python $R/bench.py --full --model swin_unetr --cpu-size 64 > $O/${T}_swin_bench.json 2> $O/${T}_swin_bench.err
+python $R/bench.py --full --aug 1 --no-cpu-baseline > $O/${T}_resunet_aug_bench.json 2> $O/${T}_resunet_aug_bench.err
 timeout 600 python $R/tools/stream_bench.py --json $O/${T}_stream.json > $O/${T}_stream.txt 2>&1
 cd /tmp; export TMPDIR=/tmp
 rm -rf /tmp/pf_graph /tmp/pf_eager

@@ -12,7 +12,7 @@ if [[ " $* " == *" suite "* ]]; then
   python -c "import __graft_entry__ as g; g.smoke()" > $O/${T}_smoke.log 2>&1; tail -3 $O/${T}_smoke.log
 fi
 # the driver's command: headline + roofline + cpu_baseline + secondary (MedFormer, SwinUNETR, --aug 1 in the same process)
-( time python $R/bench.py ) > $O/${T}_resunet_bench.json 2> $O/${T}_resunet_bench.err
+( time python $R/bench.py --full ) > $O/${T}_resunet_bench.json 2> $O/${T}_resunet_bench.err
 head -c 600 $O/${T}_resunet_bench.json; echo; tail -4 $O/${T}_resunet_bench.err
 python - <<PY
 import json
