@@ -46,6 +46,12 @@ class MapGemmDesc(C.Structure):
                 ("Xn", C.c_void_p), ("rstd_out", C.c_void_p), ("XH", C.c_void_p), ("rstd_in", C.c_void_p)]
 
 
+class SurfaceDesc(C.Structure):
+    """cbim_surface_desc of include/cbim_hip.h (one present class of the surface-distance metrics)."""
+    _fields_ = [(n, C.c_int32) for n in ("cls", "z0", "y0", "x0", "nz", "ny", "nx", "_pad")] + \
+               [("off", C.c_int64), ("list_off", C.c_int64 * 2), ("list_cap", C.c_int64 * 2)]
+
+
 # name -> (restype, argtypes)   (mirrors include/cbim_hip.h one to one)
 _SIGS = {
     "cbim_version": (i32, []),
@@ -155,6 +161,8 @@ _SIGS = {
     "cbim_softmax_accumulate": (i32, [vp, vp, vp] + [i32] * 11 + [vp]),
     "cbim_prob_finalize": (i32, [vp, vp, vp, i32, i32, i64, vp]),
     "cbim_dice_counts": (i32, [vp, i32, vp, i32, i64, i64, i32, vp, vp]),
+    "cbim_surface_scan": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "cbim_surface_lists": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, i64, f64, f64, f64, vp, vp, vp, vp, vp, i64, vp, vp]),
     "cbim_gate_fwd": (i32, [i32, vp, vp, vp, i64, i32, vp]),
     "cbim_gate_bwd": (i32, [i32, vp, vp, vp, vp, vp, i64, i32, vp]),
     "cbim_layernorm_fwd": (i32, [vp, vp, vp, f32, i32, vp, vp, i64, i32, vp]),

@@ -3,8 +3,14 @@
 The reference sums 0/1 masks in float32; those sums are integers, counted exactly on the GPU
 (``cbim_dice_counts``) — the float32 arithmetic around them (the +1e-5 terms, including the reference's
 double application in ``calculate_dice_split``) is replayed on the tiny per-class vectors, so results are
-bit-identical to the reference's.  ``calculate_distance`` (ASD/HD, CPU surface metrics) is outside the hot path.
+bit-identical to the reference's.
+
+``calculate_distance`` (ASD / HD95, metric/utils.py:8-29) gets its surface points and distances from the device
+(``metric.surface``) and replays the reference's float64 tail — area lookup, sort, sums, cumulative sums — in numpy on the
+compacted lists, in the reference's sequential order.  The neighbour-code -> surfel-area table is an input: it is a literal of
+the reference's ``metric/lookup_tables.py`` and is not part of this package (see ``area_table=``).
 """
+import numpy as np
 import torch
 
 from .. import _lib
@@ -51,3 +57,57 @@ def calculate_dice_split(pred, target, C, block_size=64 * 64 * 64):
         total_sum += summ
     dice = 2 * total_intersection / (total_sum + 1e-5)
     return dice, total_intersection, total_sum
+
+
+def _area_table(area_table, spacing_np):
+    if area_table is None:
+        try:
+            from metric import lookup_tables          # the host project the engine is plugged into
+        except ImportError as e:
+            raise ImportError("cbim_amd: calculate_distance needs the neighbour-code -> surfel-area table; `metric.lookup_tables` "
+                              "of the host project is not importable, so pass it with the `area_table=` argument (256 float64 "
+                              "values for this spacing, or a callable spacing -> table)") from e
+        area_table = lookup_tables.create_table_neighbour_code_to_surface_area
+    if callable(area_table):
+        area_table = area_table(spacing_np)
+    table = np.asarray(area_table, dtype=np.float64)
+    if table.shape != (256,):
+        raise ValueError(f"area_table must hold 256 values, got shape {table.shape}")
+    return table
+
+
+def _sorted_surfels(distances, codes, table):
+    """_sort_distances_surfels (metric/metrics.py:237-259): sorted by the pair (distance, area)."""
+    areas = table[codes]
+    order = np.lexsort((areas, distances))
+    return distances[order], areas[order]
+
+
+def _percentile_distance(distances, areas, percent):
+    """One direction of compute_robust_hausdorff (metric/metrics.py:683-713)."""
+    if len(distances) == 0:
+        return np.inf
+    cum = np.cumsum(areas) / np.sum(areas)
+    idx = np.searchsorted(cum, percent / 100.0)
+    return distances[min(idx, len(distances) - 1)]
+
+
+def calculate_distance(label_pred, label_true, spacing, C, percentage=95, *, area_table=None):
+    """metric/utils.py:8-29: (ASD_list, HD_list), numpy float64 [C-1], for classes 1 .. C-1 of two [D, H, W] label volumes
+    (device or host, int8 or int64); ``nan`` (ASD) / ``inf`` (HD) where a side is empty, as in the reference.
+    spacing: tensor or sequence of 3 (a plain sequence is taken as float32, the dtype the reference's datasets deliver).
+    area_table: 256 float64 surfel areas indexed by neighbour code for this spacing, or a callable spacing -> table; None
+    imports ``metric.lookup_tables`` from the host project and raises ImportError when it is absent."""
+    from .surface import spacing_array, surface_distances
+    lists = surface_distances(label_pred, label_true, spacing, C)
+    table = _area_table(area_table, spacing_array(spacing))
+    ASD_list = np.zeros(C - 1)
+    HD_list = np.zeros(C - 1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for i, s in enumerate(lists):
+            d_gp, a_g = _sorted_surfels(s["distances_gt_to_pred"], s["codes_gt"], table)
+            d_pg, a_p = _sorted_surfels(s["distances_pred_to_gt"], s["codes_pred"], table)
+            # compute_average_surface_distance (metric/metrics.py:625-635)
+            ASD_list[i] = (np.sum(d_gp * a_g) / np.sum(a_g) + np.sum(d_pg * a_p) / np.sum(a_p)) / 2
+            HD_list[i] = max(_percentile_distance(d_gp, a_g, percentage), _percentile_distance(d_pg, a_p, percentage))
+    return ASD_list, HD_list

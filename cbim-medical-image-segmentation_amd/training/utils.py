@@ -121,3 +121,13 @@ def exp_lr_scheduler_with_warmup(optimizer, init_lr, epoch, warmup_epoch, max_ep
     for group in optimizer.param_groups:
         group["lr"] = lr
     return lr
+
+
+@torch.no_grad()
+def concat_all_gather(tensor):
+    """training/utils.py:110-119 of the reference: all_gather over the default process group, concatenated along dim 0 in rank
+    order (no gradient flows through it)."""
+    import torch.distributed as dist
+    tensors_gather = [torch.ones_like(tensor) for _ in range(dist.get_world_size())]
+    dist.all_gather(tensors_gather, tensor, async_op=False)
+    return torch.cat(tensors_gather, dim=0)

@@ -586,6 +586,44 @@ int cbim_prob_finalize(float* prob_sum, const float* counter, int64_t* labels, i
 int cbim_dice_counts(const void* pred, int pred_bytes, const void* target, int target_bytes, int64_t N,
                      int64_t block, int C, int32_t* counts, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Surface-distance metrics (ASD / HD95) — the reference's metric/metrics.py compute_surface_distances for every
+ * foreground class of two label volumes [D][H][W] (int8 or int64), csrc/surface_kernels.hip.
+ *
+ * A corner point (z, y, x), 0 <= z <= D ..., has the 8 voxels (z-1..z, y-1..y, x-1..x) around it (outside the volume: not
+ * in any mask); its neighbour code for a mask carries bit 128 for voxel (z-1, y-1, x-1) down to bit 1 for voxel (z, y, x),
+ * and it is a surface point of the mask when the code is neither 0 nor 255.  The reference's padded bounding-box crop of
+ * `gt | pred` is exactly the box of the surface points of both masks, so:
+ *
+ *   cbim_surface_scan  : one pass over both volumes; box int32 [C][8] = per class (zmin, ymin, xmin, zmax, ymax, xmax) of
+ *                        its surface points over both masks (INT32_MAX / -1 when it has none), then the number of
+ *                        surface points of the gt mask and of the pred mask.  Row 0 (background) is left at "none".
+ *   cbim_surface_lists : for the `n` classes described by `desc` (one record per class present in either mask; the same
+ *                        records in host memory `desc_host`, from which grids are sized and every offset is range-checked,
+ *                        and in device memory `desc_dev`), four launches: neighbour codes of both masks over the class's
+ *                        box; the exact Euclidean distance transform of each surface map by a nearest-surface scan along
+ *                        x and brute-force min-plus passes along y and z carrying the integer offsets to the nearest
+ *                        surface point; the z pass evaluates only surface points of the OTHER mask and appends
+ *                        (distance, own code) to that mask's list: dist = sqrt(((dz*s0)^2 + (dy*s1)^2) + (dx*s2)^2) in
+ *                        float64 (scipy's distance_transform_edt order), +inf when the other mask has no surface.
+ *                        Order inside a list is unspecified.  cursor int32 [n][2] receives the list lengths (zeroed here).
+ *   Workspaces (caller-allocated): codes uint8 [2][vtot], dx int16 [2][vtot], dyx int32 [2][vtot] with vtot the sum
+ *   of the box volumes; mask 0 = gt, 1 = pred.  Box extents must stay below 32767.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct cbim_surface_desc {
+  int32_t cls, z0, y0, x0;     /* class label; first corner point of the box */
+  int32_t nz, ny, nx, pad_;    /* box extents in corner points */
+  int64_t off;                 /* first element of this class inside each [vtot] workspace plane */
+  int64_t list_off[2];         /* first entry of the gt / pred surface list in out_dist / out_code */
+  int64_t list_cap[2];         /* their capacities (the counts cbim_surface_scan returned) */
+} cbim_surface_desc;
+int cbim_surface_scan(const void* pred, int pred_bytes, const void* gt, int gt_bytes, int D, int H, int W, int C,
+                      int32_t* box, void* stream);
+int cbim_surface_lists(const void* pred, int pred_bytes, const void* gt, int gt_bytes, int D, int H, int W,
+                       const cbim_surface_desc* desc_host, const cbim_surface_desc* desc_dev, int n, int64_t vtot,
+                       double s0, double s1, double s2, uint8_t* codes, int16_t* dx, int32_t* dyx,
+                       double* out_dist, uint8_t* out_code, int64_t out_entries, int32_t* cursor, void* stream);
+
 /* Attention gate of AttentionUNet (/root/reference/model/dim3/attention_unet_utils.py:28-35): y = x * psi with one psi
  * per voxel (float [rows]); backward dx = dy*psi, dpsi[row] = sum_c dy*x. */
 int cbim_gate_fwd(int dtype, const void* x, const float* psi, void* y, int64_t rows, int C, void* stream);
