@@ -52,6 +52,11 @@ class SurfaceDesc(C.Structure):
                [("off", C.c_int64), ("list_off", C.c_int64 * 2), ("list_cap", C.c_int64 * 2)]
 
 
+class IndexMap(C.Structure):
+    """cbim_index_map of include/cbim_hip.h (row-major 3x4 output index -> continuous input index, passed by value)."""
+    _fields_ = [("m", C.c_double * 12)]
+
+
 # name -> (restype, argtypes)   (mirrors include/cbim_hip.h one to one)
 _SIGS = {
     "cbim_version": (i32, []),
@@ -163,6 +168,11 @@ _SIGS = {
     "cbim_dice_counts": (i32, [vp, i32, vp, i32, i64, i64, i32, vp, vp]),
     "cbim_surface_scan": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp]),
     "cbim_surface_lists": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, i64, f64, f64, f64, vp, vp, vp, vp, vp, i64, vp, vp]),
+    "cbim_order_stats_workspace": (sz, []),
+    "cbim_order_stats_f32": (i32, [vp, i64, C.POINTER(C.c_int64), i32, vp, vp, sz, vp]),
+    "cbim_bspline3_prefilter": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "cbim_resample3d": (i32, [i32, vp, vp, i32] + [i32] * 7 + [IndexMap, C.c_uint32, vp]),
+    "cbim_ensemble_finalize": (i32, [vp, vp, vp, vp, i32, i64, i32, i32, vp]),
     "cbim_gate_fwd": (i32, [i32, vp, vp, vp, i64, i32, vp]),
     "cbim_gate_bwd": (i32, [i32, vp, vp, vp, vp, vp, i64, i32, vp]),
     "cbim_layernorm_fwd": (i32, [vp, vp, vp, f32, i32, vp, vp, i64, i32, vp]),

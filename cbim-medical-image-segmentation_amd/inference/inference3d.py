@@ -55,16 +55,15 @@ def inference_whole_image(net, img, args=None):
     return acc
 
 
-def inference_sliding_window(net, img, args, return_labels=False):
-    """Half-overlapping windows of args.window_size, probabilities averaged over the windows covering a voxel
-    (inference3d.py:28-99).  With return_labels also the argmax map of validation.py:44 from the same pass."""
-    _label_gate()
+def _sliding_window_accumulate(net, img, args):
+    """The window loop of inference_sliding_window up to, not including, the division by the window count: returns the summed
+    window probabilities [B, classes, D, H, W], the count [B, 1, D, H, W] (both of the volume padded up to one window) and the
+    unpadded size, or None when nothing was padded (inference3d.py:28-86)."""
     net.eval()
     B, Cc, D, H, W = img.shape
     win_d, win_h, win_w = args.window_size
-    flag = False
+    origin = None
     if D < win_d or H < win_h or W < win_w:
-        flag = True
         origin = (D, H, W)
         img = F.pad(img, (0, max(0, win_w - W), 0, max(0, win_h - H), 0, max(0, win_d - D)))
         B, Cc, D, H, W = img.shape
@@ -80,8 +79,17 @@ def inference_sliding_window(net, img, args, return_labels=False):
                     w0, w1 = split_idx(hw, W, k)
                     logits = _logits(net, img[:, :, d0:d1, h0:h1, w0:w1].contiguous())
                     _accumulate(logits, acc, counter, d0, h0, w0)
+    return acc, counter, origin
+
+
+def inference_sliding_window(net, img, args, return_labels=False):
+    """Half-overlapping windows of args.window_size, probabilities averaged over the windows covering a voxel
+    (inference3d.py:28-99).  With return_labels also the argmax map of validation.py:44 from the same pass."""
+    _label_gate()
+    acc, counter, origin = _sliding_window_accumulate(net, img, args)
+    with torch.no_grad():
         labels = _finalize(acc, counter, return_labels)
-    if flag:
+    if origin is not None:
         acc = acc[:, :, :origin[0], :origin[1], :origin[2]]
         if labels is not None:
             labels = labels[:, :origin[0], :origin[1], :origin[2]]

@@ -624,6 +624,51 @@ int cbim_surface_lists(const void* pred, int pred_bytes, const void* gt, int gt_
                        double s0, double s1, double s2, uint8_t* codes, int16_t* dx, int32_t* dyx,
                        double* out_dist, uint8_t* out_code, int64_t out_entries, int32_t* cursor, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Volume prediction below the network (csrc/predict_kernels.hip) — the reference's prediction.py:141-199 and
+ * dataset_conversion/utils.py:7-33, which run these steps on the CPU with numpy and SimpleITK.
+ *
+ *   cbim_order_stats_f32 : out[j] (device, float [n_ranks]) = the value at 0-based rank ranks[j] of the ascending order of
+ *                          x [n] (np.partition's element), 1 <= n <= 2^31, 1 <= n_ranks <= 4; `ranks` is HOST memory, read
+ *                          before the call returns.  x MUST BE FINITE-OR-INFINITE WITHOUT NaN: the kernel orders raw float
+ *                          bits (-0 right below +0; a NaN would sort by its bit pattern, not last as numpy has it).  Radix
+ *                          select, four passes over x, no sort; workspace cbim_order_stats_workspace() bytes.  The caller
+ *                          reads `out` back (a few floats) — np.percentile(x, 98) of prediction.py:169 finishes on the host.
+ *   cbim_bspline3_prefilter : interpolation coefficients of a cubic B-spline through src float [C][D][H][W], axis after axis
+ *                          (D, H, W): samples times the gain 6, causal then anti-causal recursion with the pole sqrt(3) - 2,
+ *                          mirror boundary on whole samples — ITK's BSplineDecompositionImageFilter and
+ *                          scipy.ndimage.spline_filter(order=3, mode='mirror').  coef may be src.  An axis shorter than 2
+ *                          returns CBIM_EUNSUPPORTED.
+ *   cbim_resample3d      : dst [C][Do][Ho][Wo]; output voxel (k, j, i) reads the continuous input index
+ *                          (cz, cy, cx) = map.m[a][0] k + map.m[a][1] j + map.m[a][2] i + map.m[a][3], a = z, y, x, evaluated
+ *                          in float64 in this order.  Outside -0.5 <= c < n - 0.5 on any axis (ITK's IsInsideBuffer) the
+ *                          voxel is default_bits (the element's bit pattern, low byte for 1-byte elements).
+ *                          CBIM_RESAMPLE_NEAREST: element floor(c + 0.5), a bit copy, elem_bytes 1 or 4;
+ *                          CBIM_RESAMPLE_LINEAR : float32, 2x2x2 neighbours clamped to the edge;
+ *                          CBIM_RESAMPLE_CUBIC  : float32, src holds cbim_bspline3_prefilter coefficients, 4x4x4 taps
+ *                          floor(c) - 1 .. floor(c) + 2 with mirrored indices and separable weights (x innermost).
+ *                          src and dst must not overlap.
+ *   cbim_ensemble_finalize : checkpoint-ensemble tail for model m of M (first = m == 0, last = m == M - 1):
+ *                          p = prob_sum / counter (inference/inference3d.py:88; counter NULL = 1), total = first ? p : total + p
+ *                          (prediction.py:57), and on the last model labels uint8 [S] = first maximum over the K <= 256
+ *                          classes of total (torch.max, prediction.py:59).  prob_sum float [K][S] is not modified; counter
+ *                          float [S]; total float [K][S] may be NULL only when first && last.
+ * ------------------------------------------------------------------------------------------ */
+#define CBIM_RESAMPLE_NEAREST 0
+#define CBIM_RESAMPLE_LINEAR 1
+#define CBIM_RESAMPLE_CUBIC 3
+typedef struct cbim_index_map {
+  double m[12];                /* row-major [3][4]: rows = input z, y, x; columns = output k, j, i, constant */
+} cbim_index_map;
+size_t cbim_order_stats_workspace(void);
+int cbim_order_stats_f32(const float* x, int64_t n, const int64_t* ranks, int n_ranks, float* out, void* workspace,
+                         size_t ws_bytes, void* stream);
+int cbim_bspline3_prefilter(const float* src, float* coef, int C, int D, int H, int W, void* stream);
+int cbim_resample3d(int mode, const void* src, void* dst, int elem_bytes, int C, int Di, int Hi, int Wi, int Do, int Ho,
+                    int Wo, cbim_index_map map, uint32_t default_bits, void* stream);
+int cbim_ensemble_finalize(const float* prob_sum, const float* counter, float* total, uint8_t* labels, int K, int64_t S,
+                           int first, int last, void* stream);
+
 /* Attention gate of AttentionUNet (/root/reference/model/dim3/attention_unet_utils.py:28-35): y = x * psi with one psi
  * per voxel (float [rows]); backward dx = dy*psi, dpsi[row] = sum_c dy*x. */
 int cbim_gate_fwd(int dtype, const void* x, const float* psi, void* y, int64_t rows, int C, void* stream);
