@@ -173,6 +173,11 @@ _SIGS = {
     "cbim_bspline3_prefilter": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "cbim_resample3d": (i32, [i32, vp, vp, i32] + [i32] * 7 + [IndexMap, C.c_uint32, vp]),
     "cbim_ensemble_finalize": (i32, [vp, vp, vp, vp, i32, i64, i32, i32, vp]),
+    "cbim_components_workspace_bytes": (i64, [i32, i32, i32]),
+    "cbim_components_label": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    "cbim_components_sizes": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+    "cbim_components_filter": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "cbim_components_number": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "cbim_gate_fwd": (i32, [i32, vp, vp, vp, i64, i32, vp]),
     "cbim_gate_bwd": (i32, [i32, vp, vp, vp, vp, vp, i64, i32, vp]),
     "cbim_layernorm_fwd": (i32, [vp, vp, vp, f32, i32, vp, vp, i64, i32, vp]),

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .inference import inference3d
+from .inference.components import filter_components
 from .inference.resample import IDENTITY, _device, percentile, resample_label_to_ref, resample_xyz_axis
 from .inference.utils import get_inference
 from .model.utils import get_model
@@ -140,28 +141,40 @@ def preprocess(img, spacing, target_spacing, args, normalize="percentile"):
     return pad_to_training_size(img, args)
 
 
-def postprocess(label, original_idx, geom, ref_geom, ref_shape, args):
+def _filter_components(label, components):
+    unknown = set(components) - {"keep_largest", "min_size", "connectivity"}
+    if unknown:
+        raise ValueError(f"components: unknown keys {sorted(unknown)}")
+    return filter_components(label.contiguous(), **components)
+
+
+def postprocess(label, original_idx, geom, ref_geom, ref_shape, args, components=None):
     """prediction.py:180-199: cut the padding off and, when the training spacing is not the scan's, bring the label map back onto
     the scan's grid by nearest neighbour.  geom: the geometry of the label map (None: args.target_spacing with the scan's origin
-    and direction, as the reference sets it); ref_geom / ref_shape: the scan's.  Returns uint8 [*ref_shape] on the device."""
+    and direction, as the reference sets it); ref_geom / ref_shape: the scan's.  components (not in the reference): None, or
+    {"keep_largest": ..., "min_size": ..., "connectivity": ...} for ``inference.components.filter_components``, applied last, on
+    the scan's own grid.  Returns uint8 [*ref_shape] on the device."""
     _check_dim(args)
     label = unpad_img(torch.as_tensor(label).to(torch.uint8), original_idx, args)
     if geom is None:
         geom = (tuple(args.target_spacing), ref_geom[1], ref_geom[2])
     if tuple(geom[0]) != tuple(ref_geom[0]):
         label = resample_label_to_ref(label, geom, ref_geom, ref_shape)
+    if components is not None:
+        label = _filter_components(label, components)
     return label
 
 
-def predict_volume(model_list, img, spacing, args, origin=(0.0, 0.0, 0.0), direction=IDENTITY, normalize="percentile"):
+def predict_volume(model_list, img, spacing, args, origin=(0.0, 0.0, 0.0), direction=IDENTITY, normalize="percentile",
+                   components=None):
     """The loop body of the reference's __main__ (prediction.py:277-286) for one raw scan: preprocess, prediction, postprocess.
     img float32 [D, H, W], spacing (x, y, z); args.target_spacing is the training spacing.  Returns the uint8 label map on the
-    scan's own grid, on the device."""
+    scan's own grid, on the device; with ``components`` (see postprocess) after connected-component clean-up on that grid."""
     ref_geom = (tuple(spacing), tuple(origin), tuple(direction))
     ref_shape = tuple(int(v) for v in img.shape)
     tensor_img, original_idx = preprocess(img, spacing, args.target_spacing, args, normalize=normalize)
     label = prediction(model_list, tensor_img, args)
-    return postprocess(label, original_idx, None, ref_geom, ref_shape, args)
+    return postprocess(label, original_idx, None, ref_geom, ref_shape, args, components=components)
 
 
 def init_model(args):

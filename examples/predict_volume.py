@@ -1,6 +1,7 @@
 """Predict one volume: a raw float32 scan as .npy plus its spacing in, a uint8 label map on the scan's own grid as .npy out.
     python examples/predict_volume.py --img scan.npy --spacing 0.8,0.8,2.5 --load a.pth,b.pth --out label.npy \\
         [--target_spacing 1,1,1] [--classes 16] [--base_chan 32] [--training_size 128,128,128] [--ema] [--fp32]
+        [--keep-largest all|1,2,6] [--min-size 50]
 The checkpoints are the reference trainer's (`model_state_dict` / `ema_model_state_dict`) of a ResUNet; several of them form an
 ensemble.  NIfTI reading and writing stay with the caller (origin and direction only matter when they differ between grids)."""
 import argparse
@@ -29,6 +30,8 @@ def main():
     ap.add_argument("--training_size", type=ints, default=[128, 128, 128])
     ap.add_argument("--ema", action="store_true")
     ap.add_argument("--fp32", action="store_true")
+    ap.add_argument("--keep-largest", default=None, help="'all' or class values, ',' separated: keep only their largest component")
+    ap.add_argument("--min-size", type=int, default=0, help="drop connected components below this many voxels")
     args = ap.parse_args()
     args.dimension, args.model, args.in_chan, args.norm, args.block = "3d", "resunet", 1, "in", "BasicBlock"
     args.down_scale, args.kernel_size = [[2, 2, 2]] * 4, [[3, 3, 3]] * 5
@@ -36,7 +39,11 @@ def main():
     cbim_amd.set_compute_dtype("fp32" if args.fp32 else "bf16")
     models = init_model(args)
     img = torch.from_numpy(np.load(args.img).astype(np.float32))
-    label = predict_volume(models, img, args.spacing, args)
+    components = None
+    if args.keep_largest or args.min_size:
+        keep = () if not args.keep_largest else ("all" if args.keep_largest == "all" else ints(args.keep_largest))
+        components = {"keep_largest": keep, "min_size": args.min_size}
+    label = predict_volume(models, img, args.spacing, args, components=components)
     np.save(args.out, label.cpu().numpy())
     print(f"{args.img}: {tuple(img.shape)} at {args.spacing} mm -> {args.out} uint8, classes present {np.unique(label.cpu().numpy()).tolist()}")
 

@@ -669,6 +669,38 @@ int cbim_resample3d(int mode, const void* src, void* dst, int elem_bytes, int C,
 int cbim_ensemble_finalize(const float* prob_sum, const float* counter, float* total, uint8_t* labels, int K, int64_t S,
                            int first, int last, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Connected components of a predicted label map and the clean-up built on them (csrc/components_kernels.hip).  The
+ * reference has no such step; the semantics are scipy.ndimage.label's, applied to every class at once.
+ *
+ * labels uint8 [D][H][W] contiguous.  Two voxels are connected iff they are neighbours under `connectivity` (6, 18 or 26)
+ * and carry the same non-zero value; voxels of value 0 belong to no component.  Linear indices are int32: a volume of 2^31
+ * voxels or more is refused with CBIM_EINVAL, as are a connectivity other than 6 / 18 / 26 and null or misaligned pointers
+ * (int32 arrays 4 bytes, best 8 bytes).  Every output is a function of the input alone (bitwise reproducible).
+ *
+ *   cbim_components_workspace_bytes : bytes of cbim_components_number's scratch, CBIM_EINVAL (negative) for a refused volume.
+ *   cbim_components_label  : parent int32 [N] = linear index of the FIRST voxel in raster order of the voxel's component
+ *                            (the root; parent[root] == root), -1 for background.  Up to three launches: per-tile
+ *                            union-find in LDS, lock-free merge across tile faces with global atomicMin, flatten.
+ *   cbim_components_sizes  : size int32 [N]: size[root] = voxels of the component, 0 elsewhere; best uint64 [256]:
+ *                            best[c] = max over the roots of class c of (size << 32) | (0xFFFFFFFF - root), i.e. the largest
+ *                            component of the class, ties to the one whose first voxel comes first; 0 for an absent class.
+ *   cbim_components_filter : out[i] = labels[i] if the voxel survives, else 0, over N voxels.  A voxel of class c survives iff
+ *                            (!keep_largest[c] or its root is best[c]'s) and size[root] >= min_size[c]; keep_largest
+ *                            uint8 [256], min_size int32 [256] (device memory; entry 0 unused).  out may alias labels.
+ *   cbim_components_number : comp int32 [N] = 1-based id of the voxel's component, ids in raster order of the roots
+ *                            (scipy.ndimage.label's numbering), 0 for background; *n_out (device) = number of components.
+ *   None of them synchronises or allocates; all launches go to `stream` and can be captured in a graph.
+ * ------------------------------------------------------------------------------------------ */
+int64_t cbim_components_workspace_bytes(int D, int H, int W);
+int cbim_components_label(const uint8_t* labels, int D, int H, int W, int connectivity, int32_t* parent, void* stream);
+int cbim_components_sizes(const uint8_t* labels, const int32_t* parent, int D, int H, int W, int32_t* size, uint64_t* best,
+                          void* stream);
+int cbim_components_filter(const uint8_t* labels, const int32_t* parent, const int32_t* size, const uint64_t* best,
+                           const uint8_t* keep_largest, const int32_t* min_size, uint8_t* out, int64_t N, void* stream);
+int cbim_components_number(const int32_t* parent, int D, int H, int W, int32_t* comp, int32_t* n_out, void* scratch,
+                           void* stream);
+
 /* Attention gate of AttentionUNet (/root/reference/model/dim3/attention_unet_utils.py:28-35): y = x * psi with one psi
  * per voxel (float [rows]); backward dx = dy*psi, dpsi[row] = sum_c dy*x. */
 int cbim_gate_fwd(int dtype, const void* x, const float* psi, void* y, int64_t rows, int C, void* stream);
