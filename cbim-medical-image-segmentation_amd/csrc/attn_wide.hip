@@ -13,12 +13,7 @@
 // records, dq_m / dv_m partials) stage the voxel-side chunk in LDS and give each thread one or two codes.
 // Every sum has a fixed order: results are bit-reproducible.
 #include "cbim_common.h"
-
-#ifdef CBIM_EMU
-#define CBIM_DYN_SMEM(name) unsigned char* name = cbim_emu::dyn_smem()
-#else
-#define CBIM_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
-#endif
+#include "gfx950_prims.h"
 
 namespace cbim {
 

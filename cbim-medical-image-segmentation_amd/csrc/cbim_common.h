@@ -41,6 +41,9 @@ namespace cbim {
 typedef uint16_t bf16_t;  // raw bfloat16 bits
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -62,13 +65,12 @@ __device__ __forceinline__ bf16_t f2bf(float f) {  // round-to-nearest-even, NaN
 // packed right before their MFMA were read stale (inf/NaN rows on hardware only).
 #ifndef CBIM_EMU
 typedef __bf16 cbim_bf2_t __attribute__((ext_vector_type(2)));
-typedef float cbim_f2_t __attribute__((ext_vector_type(2)));
 #endif
 __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
 #ifdef CBIM_EMU
   return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
 #else
-  cbim_f2_t f = {lo, hi};
+  f32x2 f = {lo, hi};
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, cbim_bf2_t));
 #endif
 }
@@ -152,6 +154,20 @@ __device__ __forceinline__ float act_grad(float x, int act) {
     case CBIM_ACT_ELU: return x > 0.f ? 1.f : __expf(x);
     default: return 1.f;
   }
+}
+// ACT as a template parameter, so a hot ReLU instantiation carries no erf/exp code (code size -> instruction cache);
+// ACT < 0 = runtime switch on `rt` for the rarely used activations.
+template <int ACT> __device__ __forceinline__ float act_fwd_t(float x, int rt) {
+  if (ACT == CBIM_ACT_RELU) return x > 0.f ? x : 0.f;
+  if (ACT == CBIM_ACT_LRELU) return x > 0.f ? x : 0.01f * x;
+  if (ACT == CBIM_ACT_NONE) return x;
+  return act_fwd(x, rt);
+}
+template <int ACT> __device__ __forceinline__ float act_grad_t(float x, int rt) {
+  if (ACT == CBIM_ACT_RELU) return x > 0.f ? 1.f : 0.f;
+  if (ACT == CBIM_ACT_LRELU) return x > 0.f ? 1.f : 0.01f;
+  if (ACT == CBIM_ACT_NONE) return 1.f;
+  return act_grad(x, rt);
 }
 
 // ---- wave64 reductions ---------------------------------------------------------------------------

@@ -9,7 +9,7 @@
 //   K loop:     Cin in chunks of 64 BYTES per voxel (32 bf16 / 16 f32 channels); a "unit" is one
 //               (tile, chunk), a "stage" one kd-plane (kH*kW taps) of a unit.
 //   Pipeline:   * weights of stage s+1 stream into the other half of a double LDS buffer by LDS-DMA
-//                 (global_load_lds_dwordx4: pre-packed in MFMA B-fragment order, so the copy is
+//                 (lds_dma16: pre-packed in MFMA B-fragment order, so the copy is
 //                 contiguous and needs no registers) while stage s computes;
 //               * the input halo of unit u+1 is loaded into registers during the last stage of unit
 //                 u and written to LDS — InstanceNorm + activation of the producer applied on the way
@@ -28,6 +28,7 @@
 // Replaces aten::convolution / convolution_backward(input) for nn.Conv3d in ConvNormAct
 // (conv_layers.py:29-38), stride 1, groups 1, bias-free; padding k//2 (unet_utils.py:13).
 #include "cbim_common.h"
+#include "gfx950_prims.h"
 #include "conv_r32.h"
 #include <stdlib.h>
 
@@ -87,95 +88,7 @@ template <> struct Mma<float> {
   }
 };
 
-// ACT is a template parameter so the hot ReLU instantiation carries no erf/exp code (code size ->
-// instruction cache); ACT < 0 = runtime switch for the rarely used activations.
-template <int ACT> __device__ __forceinline__ float actf(float x, int rt) {
-  if (ACT == CBIM_ACT_RELU) return x > 0.f ? x : 0.f;
-  if (ACT == CBIM_ACT_LRELU) return x > 0.f ? x : 0.01f * x;
-  if (ACT == CBIM_ACT_NONE) return x;
-  return act_fwd(x, rt);
-}
-template <int ACT> __device__ __forceinline__ float actg(float x, int rt) {
-  if (ACT == CBIM_ACT_RELU) return x > 0.f ? 1.f : 0.f;
-  if (ACT == CBIM_ACT_LRELU) return x > 0.f ? 1.f : 0.01f;
-  if (ACT == CBIM_ACT_NONE) return 1.f;
-  return act_grad(x, rt);
-}
-
-#ifdef CBIM_EMU
-#define CBIM_SCHED_FENCE() ((void)0)
-#else
-#define CBIM_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
-
-#ifdef CBIM_EMU
-#define CBIM_DYN_SMEM(name) unsigned char* name = cbim_emu::dyn_smem()
-#else
-#define CBIM_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
-#endif
-
-// LDS-DMA: lane l copies 16 bytes from its own global address to (wave-uniform LDS base) + 16*l.
-__device__ __forceinline__ void dma16(const unsigned char* gsrc, unsigned char* lds_wave_base) {
-#ifdef CBIM_EMU
-  emu_global_load_lds16(gsrc, lds_wave_base);
-#else
-  // Issued through inline asm ON PURPOSE: with the builtin the compiler knows an LDS-DMA is in flight, treats the
-  // LGKM counter as out-of-order and turns every `s_waitcnt lgkmcnt(n)` of the fragment pipeline into
-  // lgkmcnt(0) — each MFMA pair then waits a full LDS round trip.  The DMA's completion is covered by the
-  // explicit wait_vm0() + workgroup barrier at the end of every stage.
-  unsigned a = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds_wave_base;
-  a = __builtin_amdgcn_readfirstlane(a);
-  // M0 (the LDS base of the instruction) is saved and restored INSIDE the statement: no reserved register in the clobber
-  // list (clang: "may lead to undefined behaviour"), nothing about M0 is hidden from the compiler
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "s"(a), "v"(gsrc) : "memory");
-#endif
-}
-// wave-level rendez-vous for LDS data exchanged between lanes of ONE wave (LDS executes a wave's
-// instructions in order; the compiler must not reorder across it)
-__device__ __forceinline__ void wave_sync() {
-#ifdef CBIM_EMU
-  int z = 0;
-  (void)cbim_emu::wave_exchange(&z, sizeof(z));
-#else
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#endif
-}
-__device__ __forceinline__ void wait_vm0() {
-#ifndef CBIM_EMU
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-}
-// wait for everything older than the UH halo prefetch loads issued last (vector-memory loads return in order):
-// the weight DMA of the next stage must have landed, the next tile's halo may stay in flight
-template <int N> __device__ __forceinline__ void wait_vm_halo() {
-  static_assert(N == 8 || N == 10, "wait_vm_halo: add the immediate");
-#ifndef CBIM_EMU
-  if (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-#endif
-}
-
-// 24-bit integer multiply-add (full rate; the generic 32-bit multiply is quarter rate) and an optimisation barrier
-// that makes a loop-invariant register look freshly computed
-__device__ __forceinline__ unsigned mul24(unsigned a, unsigned b) {
-#ifdef CBIM_EMU
-  return a * b;
-#else
-  return __umul24(a, b);
-#endif
-}
-__device__ __forceinline__ unsigned mad24(unsigned a, unsigned b, unsigned c) { return mul24(a, b) + c; }
 __device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-__device__ __forceinline__ unsigned launder(unsigned v) {
-#ifndef CBIM_EMU
-  asm volatile("" : "+v"(v));
-#endif
-  return v;
-}
 
 template <int MT, int NTL> struct Frags { u32x4 a[MT]; u32x4 b[NTL]; };   // one k-group of one tap
 
@@ -266,7 +179,7 @@ __global__ void __launch_bounds__(NTH, NTH == 256 ? 2 : 1) k_conv_igemm(IgemmPar
         ((size_t)nb * p.n_chunks + q) * ((size_t)p.kD * stage_bytes) + (size_t)kd * stage_bytes;
     unsigned char* dst = smem + b_base + (unsigned)buf * stage_bytes;
     for (unsigned o = (unsigned)wave * 1024; o < stage_bytes; o += NW * 1024)
-      dma16(src + o + lane * 16, dst + o);
+      lds_dma16(src + o + lane * 16, dst + o);
   };
 
   // ---- halo of a unit: issue loads into registers / write them (transformed) to LDS --------------------
@@ -322,18 +235,18 @@ __global__ void __launch_bounds__(NTH, NTH == 256 ? 2 : 1) k_conv_igemm(IgemmPar
     const unsigned c_byte = c_ok ? (unsigned)(from2 ? c0 - p.cin_split : c0) * Elem<T>::SIZE : 0u;
     // row read by items that are discarded (padding, rows past the box): the box corner clamped into the tensor
     const int sd = clampi(id0, p.Di - 1) - id0, sh = clampi(ih0, p.Hi - 1) - ih0, sw = clampi(iw0, p.Wi - 1) - iw0;
-    const unsigned safe = mul24((unsigned)((sd * p.Hi + sh) * p.Wi + sw), stride_b);
+    const unsigned safe = umul24((unsigned)((sd * p.Hi + sh) * p.Wi + sw), stride_b);
     hld = 0;
 #pragma unroll
     for (int u = 0; u < UH; ++u) {
       const unsigned pk = launder(hpk[u]);
       const unsigned hd = pk & 255u, hh = (pk >> 8) & 255u, hw = (pk >> 16) & 255u;
       // every thread issues exactly UH loads (discarded items read the safe row): the stage-end wait can then
-      // leave exactly these UH loads in flight (wait_vm_halo)
+      // leave exactly these UH loads in flight (wait_vm<UH>)
       const bool ld = !(I_DBG & 1) && (pk >> 24) != 0 && c_ok && (unsigned)(id0 + (int)hd) < (unsigned)p.Di &&
                       (unsigned)(ih0 + (int)hh) < (unsigned)p.Hi && (unsigned)(iw0 + (int)hw) < (unsigned)p.Wi;
-      const unsigned rel = mad24(mad24(hd, (unsigned)p.Hi, hh), (unsigned)p.Wi, hw);
-      const unsigned voff = ld ? mad24(rel, stride_b, c_byte) : safe;
+      const unsigned rel = umad24(umad24(hd, (unsigned)p.Hi, hh), (unsigned)p.Wi, hw);
+      const unsigned voff = ld ? umad24(rel, stride_b, c_byte) : safe;
       hld |= (ld ? 1u : 0u) << u;
       hreg[u] = *(const u32x4*)(tbase + voff);
     }
@@ -357,7 +270,7 @@ __global__ void __launch_bounds__(NTH, NTH == 256 ? 2 : 1) k_conv_igemm(IgemmPar
           float f[CPC];
           Elem<T>::unpack(w, f);
 #pragma unroll
-          for (int j = 0; j < CPC; ++j) f[j] = actf<ACT>((f[j] - st[2 * j]) * st[2 * j + 1], p.act);
+          for (int j = 0; j < CPC; ++j) f[j] = act_fwd_t<ACT>((f[j] - st[2 * j]) * st[2 * j + 1], p.act);
           w = Elem<T>::pack(f);
         }
         *(u32x4*)(smem + l_base + (unsigned)(u * (NT / SLOTS) * RB) + (((unsigned)my_slot ^ ((pk >> 8) & (SLOTS - 1))) << 4)) = w;
@@ -417,7 +330,7 @@ __global__ void __launch_bounds__(NTH, NTH == 256 ? 2 : 1) k_conv_igemm(IgemmPar
   stats_publish();
   __syncthreads();
   halo_store();
-  wait_vm0();
+  wait_vm<0>();
   __syncthreads();
 
 #ifdef CBIM_IGEMM_PROF
@@ -493,7 +406,7 @@ __global__ void __launch_bounds__(NTH, NTH == 256 ? 2 : 1) k_conv_igemm(IgemmPar
           fetch(f0, 0, 0, toff, b_buf);
           // CBIM_SCHED_FENCE pins "issue the next fragments' ds_reads, THEN run the MFMAs on the previous set":
           // left to itself the scheduler sinks each ds_read next to its use (register pressure) and every
-          // MFMA pair then waits a full LDS round trip (s_waitcnt lgkmcnt(0) right after the reads).
+          // MFMA pair then waits a full LDS round trip (an lgkmcnt(0) wait right after the reads).
           for (int tp = 0; tp < ptaps; ++tp) {
             fetch(f1, tp, 1, toff, b_buf);
             CBIM_SCHED_FENCE();
@@ -520,8 +433,8 @@ __global__ void __launch_bounds__(NTH, NTH == 256 ? 2 : 1) k_conv_igemm(IgemmPar
       if (last_plane && unit + 1 < n_units) stats_publish();
       // this wave's LDS-DMA (next stage's weights) has landed; the halo prefetch issued in this stage (kd == 0)
       // keeps flying through the following stages
-      if (kd == 0 && !last_plane && unit + 1 < n_units) wait_vm_halo<UH>();
-      else wait_vm0();
+      if (kd == 0 && !last_plane && unit + 1 < n_units) wait_vm<UH>();
+      else wait_vm<0>();
       CBIM_TICK(2);
       __syncthreads();   // every wave is done with this stage's A/B reads
       CBIM_TICK(3);
@@ -577,7 +490,7 @@ __global__ void __launch_bounds__(NTH, NTH == 256 ? 2 : 1) k_conv_igemm(IgemmPar
               const int vr = (lane + 64 * it) / OCH;                 // voxel row inside the 32-voxel m-tile
               const unsigned td = ok_ & 255u, th = (ok_ >> 8) & 255u, tw = (ok_ >> 16) & 255u;
               const bool inb = c_ok && od0 + (int)td < p.Do && oh0 + (int)th < p.Ho && ow0 + (int)tw < p.Wo;
-              const unsigned rel = mad24(mad24(td, (unsigned)p.Ho, th), (unsigned)p.Wo, tw);
+              const unsigned rel = umad24(umad24(td, (unsigned)p.Ho, th), (unsigned)p.Wo, tw);
               float v[CPC];
 #pragma unroll
               for (int j4 = 0; j4 < CPC; j4 += 4) {
@@ -586,7 +499,7 @@ __global__ void __launch_bounds__(NTH, NTH == 256 ? 2 : 1) k_conv_igemm(IgemmPar
               }
               if (p.ksplit > 1) {   // split-K: raw fp32 partial, finished by k_splitk_finish
                 if (inb) {
-                  float* wp = (float*)(ws_tile + mad24(rel, ws_sb, (unsigned)cch0 * 4u));
+                  float* wp = (float*)(ws_tile + umad24(rel, ws_sb, (unsigned)cch0 * 4u));
 #pragma unroll
                   for (int j4 = 0; j4 < CPC; j4 += 4) *(f32x4*)(wp + j4) = f32x4{v[j4], v[j4 + 1], v[j4 + 2], v[j4 + 3]};
                 }
@@ -602,17 +515,17 @@ __global__ void __launch_bounds__(NTH, NTH == 256 ? 2 : 1) k_conv_igemm(IgemmPar
                 const unsigned cb = (unsigned)cch0 * Elem<T>::SIZE;
                 if (p.res) {
                   float f[CPC];
-                  Elem<T>::unpack(*(const u32x4*)(res_tile + mad24(rel, res_sb, cb)), f);
+                  Elem<T>::unpack(*(const u32x4*)(res_tile + umad24(rel, res_sb, cb)), f);
 #pragma unroll
                   for (int j = 0; j < CPC; ++j) v[j] += f[j];
                 }
                 if (p.mx) {
                   float f[CPC];
-                  Elem<T>::unpack(*(const u32x4*)(mx_tile + mad24(rel, mx_sb, cb)), f);
+                  Elem<T>::unpack(*(const u32x4*)(mx_tile + umad24(rel, mx_sb, cb)), f);
 #pragma unroll
                   for (int j = 0; j < CPC; ++j) {
                     float xh = (f[j] - mm[j]) * mr[j];
-                    v[j] *= actg<ACT>(xh, p.act);
+                    v[j] *= act_grad_t<ACT>(xh, p.act);
                     s0[j] += v[j];
                     s1[j] += v[j] * xh;
                   }
@@ -621,7 +534,7 @@ __global__ void __launch_bounds__(NTH, NTH == 256 ? 2 : 1) k_conv_igemm(IgemmPar
                   for (int j = 0; j < CPC; ++j) { float d = v[j] - sh[j]; s0[j] += d; s1[j] += d * d; }
                 }
                 cnt += 1.f;
-                if (!(I_DBG & 4)) *(u32x4*)(y_tile + mad24(rel, y_sb, cb)) = Elem<T>::pack(v);
+                if (!(I_DBG & 4)) *(u32x4*)(y_tile + umad24(rel, y_sb, cb)) = Elem<T>::pack(v);
               }
             }
           }
@@ -736,7 +649,7 @@ __global__ void __launch_bounds__(FT) k_splitk_finish(const float* __restrict__ 
 #pragma unroll
         for (int j = 0; j < CPC; ++j) {
           float xh = (f[j] - mm[j]) * mr[j];
-          a[j] *= actg<ACT>(xh, act);
+          a[j] *= act_grad_t<ACT>(xh, act);
           s0[j] += a[j];
           s1[j] += a[j] * xh;
         }

@@ -24,6 +24,7 @@
 //     chunks; residual add, activated mask, shifted moments / backward sums; one statistics record per (image, strip of row
 //     tiles), fixed merge order.
 #include "cbim_common.h"
+#include "gfx950_prims.h"
 #include "conv_r32.h"
 #include <stdlib.h>
 
@@ -46,34 +47,6 @@ struct PwParams {
   const void* w_lo;        // X32 only: the residue image of the weight (cbim_conv3d_pack_weights_lo) or NULL
 };
 
-#ifdef CBIM_EMU
-#define PW_DYN_SMEM(name) unsigned char* name = cbim_emu::dyn_smem()
-#else
-#define PW_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
-#endif
-
-__device__ __forceinline__ void pw_wave_sync() {
-#ifdef CBIM_EMU
-  int z = 0;
-  (void)cbim_emu::wave_exchange(&z, sizeof(z));
-#else
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#endif
-}
-
-template <int ACT> __device__ __forceinline__ float pw_actf(float x, int rt) {
-  if (ACT == CBIM_ACT_RELU) return x > 0.f ? x : 0.f;
-  if (ACT == CBIM_ACT_NONE) return x;
-  return act_fwd(x, rt);
-}
-template <int ACT> __device__ __forceinline__ float pw_actg(float x, int rt) {
-  if (ACT == CBIM_ACT_RELU) return x > 0.f ? 1.f : 0.f;
-  if (ACT == CBIM_ACT_NONE) return 1.f;
-  return act_grad(x, rt);
-}
-
 // grid.x = N * Pn * n_wblk (output-channel block fastest: the workgroups that share rows are neighbours in time)
 // KS = 1: a workgroup tile is 128 rows, wave w owns rows 32 w .. 32 w + 31 over the whole K.
 // KS = 4 (low-resolution layers with a long K — 8^3 1280->320 is 4 row tiles x 5 channel blocks = 20 workgroups of 80 dependent
@@ -90,7 +63,7 @@ __global__ void __launch_bounds__(PW_NT, 2) k_conv_pw(PwParams p) {
   static_assert(TK || !X32, "fp32 rows: token mode only");
   typedef bf16_tag T;
   constexpr int CPC = 8, OCH = 4, IT = 2;
-  PW_DYN_SMEM(smem);
+  CBIM_DYN_SMEM(smem);
   float* scr_all = (float*)smem;                                  // [4 waves][32 x 32] fp32
   float* red = (float*)(smem + PW_NW * 4096);                     // [4 waves][NTW * 32][3]
   float* stL = (float*)(smem + PW_NW * 4096 + PW_NW * NTW * 32 * 3 * 4);   // [Cin][2]: mean, rstd of image n
@@ -206,7 +179,7 @@ __global__ void __launch_bounds__(PW_NT, 2) k_conv_pw(PwParams p) {
               float f[CPC];
               Elem<T>::unpack(a, f);
 #pragma unroll
-              for (int j = 0; j < CPC; ++j) f[j] = pw_actf<ACT>(f[j], p.act);
+              for (int j = 0; j < CPC; ++j) f[j] = act_fwd_t<ACT>(f[j], p.act);
               a = Elem<T>::pack(f);
             }
           }
@@ -217,7 +190,7 @@ __global__ void __launch_bounds__(PW_NT, 2) k_conv_pw(PwParams p) {
               Elem<T>::unpack(a, f);
               const float* st = stL + c0 * 2;
 #pragma unroll
-              for (int j = 0; j < CPC; ++j) f[j] = pw_actf<ACT>((f[j] - st[2 * j]) * st[2 * j + 1], p.act);
+              for (int j = 0; j < CPC; ++j) f[j] = act_fwd_t<ACT>((f[j] - st[2 * j]) * st[2 * j + 1], p.act);
               a = Elem<T>::pack(f);
             }
           }
@@ -252,10 +225,10 @@ __global__ void __launch_bounds__(PW_NT, 2) k_conv_pw(PwParams p) {
 #pragma unroll
         for (int j = 0; j < CPC; ++j) bv[j] = (p.bias && c_ok) ? p.bias[cch0 + j] : 0.f;
       }
-      if (KS == 4) __syncthreads(); else pw_wave_sync();   // the previous n-tile's scratch reads are done
+      if (KS == 4) __syncthreads(); else wave_sync();   // the previous n-tile's scratch reads are done
 #pragma unroll
       for (int r = 0; r < 16; ++r) scr[((r & 3) + 8 * (r >> 2) + 4 * half) * 32 + li] = acc[nt][r];
-      if (KS == 4) __syncthreads(); else pw_wave_sync();
+      if (KS == 4) __syncthreads(); else wave_sync();
       const bool mine = KS != 4 || wave == (nt & 3);        // KS: wave (nt mod 4) adds the four partial tiles and finishes nt
 #pragma unroll
       for (int it = 0; it < IT; ++it) {
@@ -322,7 +295,7 @@ __global__ void __launch_bounds__(PW_NT, 2) k_conv_pw(PwParams p) {
 #pragma unroll
             for (int j = 0; j < CPC; ++j) {
               const float xh = (f[j] - mm[j]) * mr[j];
-              v[j] *= pw_actg<ACT>(xh, p.act);
+              v[j] *= act_grad_t<ACT>(xh, p.act);
               s0[j] += v[j];
               s1[j] += v[j] * xh;
             }
@@ -392,24 +365,6 @@ __global__ void __launch_bounds__(PW_NT, 2) k_conv_pw(PwParams p) {
 // reads (ds_read_b64_tr_b16, the fragment scheme of conv_wgrad.hip).  Strips of rows -> slabs [strip][Cout_pad][Cin_pad] -> the
 // fixed-order k_wgrad_reduce of conv_wgrad.hip.
 static constexpr int PWG_VT = 128;                    // rows per stage
-__device__ __forceinline__ u32x2 pw_lds_tr16_b64(const unsigned char* p) {
-#ifdef CBIM_EMU
-  unsigned short o[4];
-  emu_ds_read_tr16_b64(p, o);
-  u32x2 r;
-  r.x = (unsigned)o[0] | ((unsigned)o[1] << 16);
-  r.y = (unsigned)o[2] | ((unsigned)o[3] << 16);
-  return r;
-#else
-  typedef __attribute__((ext_vector_type(4))) short s16x4;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
-  u32x2 r;
-  r.x = (unsigned)(unsigned short)v.x | ((unsigned)(unsigned short)v.y << 16);
-  r.y = (unsigned)(unsigned short)v.z | ((unsigned)(unsigned short)v.w << 16);
-  return r;
-#endif
-}
 
 struct PwgParams {
   const void* x; int64_t x_stride; const float* in_stats; const void* dy; int64_t dy_stride; float* ws;
@@ -479,7 +434,7 @@ __global__ void __launch_bounds__(PW_NT, 2) k_pw_wgrad(PwgParams p) {
         float f[CPC];
         Elem<T>::unpack(xa, f);
 #pragma unroll
-        for (int j = 0; j < CPC; ++j) f[j] = pw_actf<ACT>((f[j] - mean[j]) * rstd[j], p.act);
+        for (int j = 0; j < CPC; ++j) f[j] = act_fwd_t<ACT>((f[j] - mean[j]) * rstd[j], p.act);
         xa = Elem<T>::pack(f);
       }
       *(u32x4*)(&lds[buf][sub_off][v * 64 + in_off]) = gd[u];
@@ -507,8 +462,8 @@ __global__ void __launch_bounds__(PW_NT, 2) k_pw_wgrad(PwgParams p) {
 #pragma unroll
     for (int ks = 0; ks < PWG_VT / 16; ++ks) {
       const unsigned m0 = (unsigned)(ks * 16 + mq) * 64u + colb, m1 = m0 + 4u * 64u;
-      const u32x2 a0 = pw_lds_tr16_b64(A + m0), a1 = pw_lds_tr16_b64(A + m1);
-      const u32x2 b0 = pw_lds_tr16_b64(B + m0), b1 = pw_lds_tr16_b64(B + m1);
+      const u32x2 a0 = lds_tr16_b64(A + m0), a1 = lds_tr16_b64(A + m1);
+      const u32x2 b0 = lds_tr16_b64(B + m0), b1 = lds_tr16_b64(B + m1);
       const u32x4 af = u32x4{a0.x, a0.y, a1.x, a1.y}, bf = u32x4{b0.x, b0.y, b1.x, b1.y};
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af), __builtin_bit_cast(bf16x8, bf), acc, 0, 0, 0);
     }

@@ -19,17 +19,18 @@
 //     fragment of input plane i serves (n-tile i, kd 0), (n-tile i-1, kd 1) and (n-tile i-2, kd 2), so per (kh,kw)
 //     10 fragment reads feed 24 MFMAs; reads stream through a small register ring, plane-major;
 //   * the halo (10x10x10 rows x 64 B) is DOUBLE buffered in LDS (2 x 64 KiB): the next tile's halo is fetched while
-//     this tile computes — by LDS-DMA (global_load_lds_dwordx4, no registers, no VALU) when the input is used as
+//     this tile computes — by LDS-DMA (lds_dma16, no registers, no VALU) when the input is used as
 //     it is (dgrad, or a raw convolution), through registers with InstanceNorm + activation applied on the way
 //     (pre-activation ConvNormAct, conv_layers.py:48-49; zero padding after the transform) otherwise; the per-item
 //     work is spread over the (kh,kw) steps of the MFMA loop;
 //   * the MFMA operands are swapped (A = weights, B = voxels), so an accumulator holds 4 output channels of ONE voxel
-//     per lane: one v_permlane16_swap per register between two n-tiles leaves every lane with a whole 16-byte
+//     per lane: one swap16 per register between two n-tiles leaves every lane with a whole 16-byte
 //     channel chunk of one voxel — residual add, act' mask, statistics and the store need no LDS transpose; the
 //     per-channel statistics are per-lane running sums, combined across lanes once per workgroup.
 // Same C ABI entry (cbim_conv3d_igemm picks this kernel when the layer qualifies), same packed-weight layout, same
 // partial-record format as conv_igemm.hip.
 #include "cbim_common.h"
+#include "gfx950_prims.h"
 #include "conv_r32.h"
 #include <stdlib.h>
 
@@ -79,89 +80,7 @@ template <int TD> struct RGeom {
 
 __device__ __attribute__((aligned(64))) unsigned int g_r32_zero[16];   // source of padding rows for the LDS-DMA
 
-typedef __attribute__((ext_vector_type(4))) float r_f32x4;
-
-#ifdef CBIM_EMU
-#define R_SCHED_GROUP(mask, n) ((void)0)
-#define R_SCHED_FENCE() ((void)0)
-#define R_DYN_SMEM(name) unsigned char* name = cbim_emu::dyn_smem()
-#else
-// one group of the instruction-interleave pattern of a scheduling region: `n` instructions of class `mask`
-// (0x2 VALU, 0x4 SALU, 0x8 MFMA, 0x100 DS read, 0x200 DS write) come next
-#define R_SCHED_GROUP(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
-#define R_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define R_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
-#endif
-
-__device__ __forceinline__ void r_dma16(const unsigned char* gsrc, unsigned char* lds_wave_base) {
-#ifdef CBIM_EMU
-  emu_global_load_lds16(gsrc, lds_wave_base);
-#else
-  // inline asm on purpose (conv_igemm.hip dma16): the compiler must not treat LGKM as out of order
-  unsigned a = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds_wave_base;
-  a = __builtin_amdgcn_readfirstlane(a);
-  // M0 (the LDS base of the instruction) is saved and restored INSIDE the statement: no reserved register in the clobber
-  // list (clang: "may lead to undefined behaviour"), nothing about M0 is hidden from the compiler
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "s"(a), "v"(gsrc) : "memory");
-#endif
-}
-__device__ __forceinline__ void r_wait_vm0() {
-#ifndef CBIM_EMU
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-}
-__device__ __forceinline__ unsigned r_launder(unsigned v) {
-#ifndef CBIM_EMU
-  asm volatile("" : "+v"(v));
-#endif
-  return v;
-}
-__device__ __forceinline__ unsigned r_mul24(unsigned a, unsigned b) {
-#ifdef CBIM_EMU
-  return a * b;
-#else
-  return __umul24(a, b);
-#endif
-}
-// XOR key of the 16-byte slot inside halo row (hd, hh, hw): a ds_read_b128 lane group of the B-fragment read covers the
-// two h rows of the wave's patch and two k-groups; keys 0 / 2 on alternating rows give it 16 distinct cells of the
-// 256-byte bank window (key hh & 3, right for the 4-row patches of conv_igemm.hip, measured 37 % conflict cycles here)
-__device__ __forceinline__ unsigned r_swz(unsigned hh) { return (hh & 1u) << 1; }
-// partner value of the butterfly step `msk` (1, 2, 4, 8, 16) of an all-reduce SUM over 32 lanes.  Steps 1 and 2 are quad
-// permutes, steps 4 and 8 the half-row / row mirrors of the data-parallel-primitive path (vector-ALU rate): after steps 1, 2
-// the four lanes of a quad hold the same value, so the mirror partner (other quad, any lane) is as good as lane ^ 4 —
-// bit-identical to the xor butterfly; only step 16 crosses 16-lane rows and goes through the LDS crossbar.  (All five
-// steps as ds_bpermute were 85 LDS round trips per tile in the multi-chunk epilogues.)
-template <int MSK>
-__device__ __forceinline__ float r_bfly(float v) {
-#ifdef CBIM_EMU
-  return __shfl_xor(v, MSK, 64);
-#else
-  if (MSK == 16) return __shfl_xor(v, 16, 64);
-  constexpr int ctrl = MSK == 1 ? 0xB1 : MSK == 2 ? 0x4E : MSK == 4 ? 0x141 : 0x140;   // quad_perm [1,0,3,2] / [2,3,0,1], row_half_mirror, row_mirror
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, false));
-#endif
-}
 #define R_BFLY_ROUNDS(...) { constexpr int msk = 1; __VA_ARGS__ } { constexpr int msk = 2; __VA_ARGS__ } { constexpr int msk = 4; __VA_ARGS__ } { constexpr int msk = 8; __VA_ARGS__ } { constexpr int msk = 16; __VA_ARGS__ }
-
-// exchange between 16-lane rows: a's odd rows (lanes 16..31, 48..63) <-> b's even rows (lanes 0..15, 32..47)
-// (v_permlane16_swap_b32)
-__device__ __forceinline__ void r_swap16(float& a, float& b) {
-#ifdef CBIM_EMU
-  struct P { float a, b; } mine = {a, b};
-  const P* buf = (const P*)cbim_emu::wave_exchange(&mine, sizeof(P));
-  const int l = CBIM_EMU_LANE_ID();
-  if (l & 16) a = buf[l - 16].b;
-  else b = buf[l + 16].a;
-#else
-  typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-  u2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r.x);
-  b = __uint_as_float(r.y);
-#endif
-}
 
 // TR: the input is transformed (InstanceNorm + ACT) in place in LDS after the LDS-DMA; !TR: used as it is
 // MX: dgrad epilogue (x act'(xh) mask + the two InstanceNorm-backward sums); !MX: forward epilogue (moments)
@@ -175,7 +94,7 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
   typedef RGeom<TD> G;
   constexpr int NT = G::NT, NW = G::NW, HP = G::HP, UH = G::UH;
   constexpr unsigned HBUF = G::HBUF;
-  R_DYN_SMEM(smem);
+  CBIM_DYN_SMEM(smem);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lv = lane & 15, lq = lane >> 4;
   const int tiles_per_n = p.tiles_d * p.tiles_h * p.tiles_w;
   const int n_tiles = p.N * tiles_per_n;
@@ -211,14 +130,14 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
     for (int tp = 0; tp < 27; ++tp) wf[tp] = *(const u32x4*)(wp + (size_t)tp * w_tap);
 #ifndef CBIM_EMU
     // The compiler tracks these loads as possibly pending at the loop back-edge and guards the first MFMA of every tile
-    // with s_waitcnt vmcnt(1) — which, with the LDS-DMA pieces it cannot see in flight, waits for the DMA to land.
+    // with a vmcnt(1) wait — which, with the LDS-DMA pieces it cannot see in flight, waits for the DMA to land.
     // Passing the registers through an empty asm makes it wait once, here, and forget the loads.
 #pragma unroll
     for (int tp = 0; tp < 27; ++tp) asm volatile("" : "+v"(wf[tp]));
 #endif
   }
   // B operand (voxels): fragment of plane i at tap (kh, kw) = 16 bytes at row (i, th + kh, tw + kw), slot
-  // lq ^ r_swz(th + kh); base per (h-pair, kh); plane and kw are immediates (i * 6400 + kw * 64)
+  // lq ^ halo_swz(th + kh); base per (h-pair, kh); plane and kw are immediates (i * 6400 + kw * 64)
   int thp[HP];
   unsigned fb[HP][3];
 #pragma unroll
@@ -226,11 +145,11 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
     thp[hp] = 2 * (vg * HP + hp) + (lv >> 3);
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh)
-      fb[hp][kh] = (unsigned)((thp[hp] + kh) * 10 + tw) * R_RB + (((unsigned)lq ^ r_swz((unsigned)(thp[hp] + kh))) << 4);
+      fb[hp][kh] = (unsigned)((thp[hp] + kh) * 10 + tw) * R_RB + (((unsigned)lq ^ halo_swz((unsigned)(thp[hp] + kh))) << 4);
   }
 
   // ---- halo items of this thread (the same for every tile): position inside the (TD+2)x10x10 box ---------------
-  // LDS-DMA item q = tid + NT u is PHYSICAL (LDS byte q*16 = row q>>2, slot q&3), source slot = (q&3) ^ r_swz(hh).
+  // LDS-DMA item q = tid + NT u is PHYSICAL (LDS byte q*16 = row q>>2, slot q&3), source slot = (q&3) ^ halo_swz(hh).
   // The position is decoded per tile from the laundered thread index (~10 VALU per item) instead of living in
   // registers next to the weights.
   auto item_pos = [&](unsigned tl, int u) -> unsigned {   // hd | hh << 8 | hw << 16 | exists << 24
@@ -269,9 +188,9 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
     for (int u = 0; u < UH; ++u) {
       const unsigned pk = item_pos((unsigned)tid, u);
       const unsigned hd = pk & 255u, hh = (pk >> 8) & 255u, hw = (pk >> 16) & 255u;
-      const unsigned rel = r_mul24(r_mul24(hd, (unsigned)p.Hi) + hh, (unsigned)p.Wi) + hw;
+      const unsigned rel = umul24(umul24(hd, (unsigned)p.Hi) + hh, (unsigned)p.Wi) + hw;
       // MC: row of the box (bytes = rel * row stride of the chunk's tensor); else the byte offset itself
-      tab_off[tid + NT * u] = MC ? rel : r_mul24(rel, x_sb) + ((my_slot ^ r_swz(hh)) << 4);
+      tab_off[tid + NT * u] = MC ? rel : umul24(rel, x_sb) + ((my_slot ^ halo_swz(hh)) << 4);
       tab_pos[tid + NT * u] = (unsigned short)(hd | (hh << 4) | (hw << 8) | ((pk >> 24) << 12));
     }
     // (read back by the same thread only: no barrier needed, the prologue has one anyway)
@@ -280,16 +199,16 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
   auto item_get = [&](int u, unsigned sb, unsigned& hd, unsigned& hh, unsigned& hw, bool& exists, unsigned& off) {
     unsigned rel;
     if (G::ITAB) {
-      const unsigned tl = r_launder((unsigned)tid);      // (keeps the loop-invariant reads inside the tile loop)
+      const unsigned tl = launder((unsigned)tid);      // (keeps the loop-invariant reads inside the tile loop)
       const unsigned ps = tab_pos[tl + NT * u];
       rel = tab_off[tl + NT * u];
       hd = ps & 15u; hh = (ps >> 4) & 15u; hw = (ps >> 8) & 15u; exists = (ps >> 12) != 0;
     } else {
-      const unsigned pk = item_pos(r_launder((unsigned)tid), u);
+      const unsigned pk = item_pos(launder((unsigned)tid), u);
       hd = pk & 255u; hh = (pk >> 8) & 255u; hw = (pk >> 16) & 255u; exists = (pk >> 24) != 0;
-      rel = r_mul24(r_mul24(hd, (unsigned)p.Hi) + hh, (unsigned)p.Wi) + hw;
+      rel = umul24(umul24(hd, (unsigned)p.Hi) + hh, (unsigned)p.Wi) + hw;
     }
-    off = (G::ITAB && !MC) ? rel : r_mul24(rel, sb) + ((my_slot ^ r_swz(hh)) << 4);
+    off = (G::ITAB && !MC) ? rel : umul24(rel, sb) + ((my_slot ^ halo_swz(hh)) << 4);
   };
   // source address of halo item u of tile `tp` (in range: the tensor; padding: 64 zero bytes) ---------------------
   auto item_src = [&](const TilePos& tp, int u) -> const unsigned char* {
@@ -313,7 +232,7 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
   auto dma_item = [&](const TilePos& tp, int u, unsigned buf) {
     const bool past = (wave * 64 + NT * u) >= G::PIECES * 64;     // wave-uniform
     const unsigned char* src = item_src(tp, u);                   // (items past the box: the zero page)
-    r_dma16(src, smem + (past ? (unsigned)G::PIECES * 1024u : buf + (unsigned)(wave * 64 + NT * u) * 16));
+    lds_dma16(src, smem + (past ? (unsigned)G::PIECES * 1024u : buf + (unsigned)(wave * 64 + NT * u) * 16));
   };
   // TR path: the raw halo arrives by the same LDS-DMA; a wave transforms IN PLACE exactly the 1 KiB pieces it has
   // fetched itself (lane = the piece's 16-byte item), so the only ordering needed is the wave's own counted vmcnt —
@@ -321,7 +240,6 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
   // -> bf16 pairs -> ReLU as v_pk_max_i16 against 0 -> ds_write_b128.  The statistics of the item's channel chunk
   // are one 64-byte row of a 256-byte LDS table.  Padding rows stay zero.
   auto tr_xform = [&](const TilePos& tp, int u, unsigned buf) {
-    typedef float f2_t __attribute__((ext_vector_type(2)));
     typedef short s2_t __attribute__((ext_vector_type(2)));
     const int id0 = tp.td * TD - p.pD, ih0 = tp.th * 8 - p.pH, iw0 = tp.tw * 8 - p.pW;
     unsigned hd, hh, hw, off;
@@ -331,16 +249,16 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
                     (unsigned)(iw0 + (int)hw) < (unsigned)p.Wi;
     if (exists) {                                     // (items past the box do not exist in LDS)
       unsigned char* cell = smem + buf + ((unsigned)tid + (unsigned)NT * (unsigned)u) * 16u;
-      const float* is = (const float*)(smem + ist_base) + tp.cc * 64 + ((my_slot ^ r_swz(hh)) << 4);   // logical chunk of this cell
+      const float* is = (const float*)(smem + ist_base) + tp.cc * 64 + ((my_slot ^ halo_swz(hh)) << 4);   // logical chunk of this cell
       const u32x4 raw = *(const u32x4*)cell;
       const unsigned rw[4] = {raw.x, raw.y, raw.z, raw.w};
       unsigned ow[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const f32x4 q4 = *(const f32x4*)(is + 4 * j);   // (mean, rstd) of channels 2j, 2j+1
-        const f2_t x = {__uint_as_float(rw[j] << 16), __uint_as_float(rw[j] & 0xffff0000u)};
-        const f2_t m = {q4.x, q4.z}, r = {q4.y, q4.w};
-        const f2_t y = (x - m) * r;
+        const f32x2 x = {__uint_as_float(rw[j] << 16), __uint_as_float(rw[j] & 0xffff0000u)};
+        const f32x2 m = {q4.x, q4.z}, r = {q4.y, q4.w};
+        const f32x2 y = (x - m) * r;
         unsigned o = pk_bf16(y.x, y.y);
         if (ACT == CBIM_ACT_RELU) {
           s2_t h = __builtin_bit_cast(s2_t, o);
@@ -353,24 +271,20 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
       *(u32x4*)cell = u32x4{ow[0], ow[1], ow[2], ow[3]};
     }
   };
-  auto wait_vm = [&](int n) {   // at most n vector-memory operations of this wave still in flight
-#ifndef CBIM_EMU
-    if (n >= 24) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    else if (n >= 22) asm volatile("s_waitcnt vmcnt(22)" ::: "memory");
-    else if (n >= 20) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-    else if (n >= 18) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-    else if (n >= 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if (n >= 14) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-    else if (n >= 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if (n >= 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else if (n >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (n >= 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if (n >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if (n >= 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-    (void)n;
-#endif
+  auto wait_vm_rt = [&](int n) {   // wait_vm<N> for a run-time n, rounded down to even, 24 at the most
+    if (n >= 24) wait_vm<24>();
+    else if (n >= 22) wait_vm<22>();
+    else if (n >= 20) wait_vm<20>();
+    else if (n >= 18) wait_vm<18>();
+    else if (n >= 16) wait_vm<16>();
+    else if (n >= 14) wait_vm<14>();
+    else if (n >= 12) wait_vm<12>();
+    else if (n >= 10) wait_vm<10>();
+    else if (n >= 8) wait_vm<8>();
+    else if (n >= 6) wait_vm<6>();
+    else if (n >= 4) wait_vm<4>();
+    else if (n >= 2) wait_vm<2>();
+    else wait_vm<0>();
   };
 
   // ---- per-lane statistics: after the epilogue exchange a lane owns channel chunk cidx = 2*ch + (lq >> 1) -------
@@ -393,8 +307,8 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
     float* red = (float*)(smem + red_base);
     R_BFLY_ROUNDS(
       float u0[8], u1[8];
-      _Pragma("unroll") for (int j = 0; j < 8; ++j) { u0[j] = r_bfly<msk>(t0[j]); u1[j] = r_bfly<msk>(t1[j]); }
-      const float tc = r_bfly<msk>(tcnt);
+      _Pragma("unroll") for (int j = 0; j < 8; ++j) { u0[j] = dpp_bfly<msk>(t0[j]); u1[j] = dpp_bfly<msk>(t1[j]); }
+      const float tc = dpp_bfly<msk>(tcnt);
       _Pragma("unroll") for (int j = 0; j < 8; ++j) { t0[j] += u0[j]; t1[j] += u1[j]; }
       tcnt += tc;
     )
@@ -418,8 +332,8 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
     if (!LS) {
     R_BFLY_ROUNDS(                             // lanes differing in bits 0..4 (voxel, lq & 1) hold the same channels
       float t0[8], t1[8];
-      _Pragma("unroll") for (int j = 0; j < 8; ++j) { t0[j] = r_bfly<msk>(s0[j]); t1[j] = r_bfly<msk>(s1[j]); }
-      const float tc = r_bfly<msk>(cnt);
+      _Pragma("unroll") for (int j = 0; j < 8; ++j) { t0[j] = dpp_bfly<msk>(s0[j]); t1[j] = dpp_bfly<msk>(s1[j]); }
+      const float tc = dpp_bfly<msk>(cnt);
       _Pragma("unroll") for (int j = 0; j < 8; ++j) { s0[j] += t0[j]; s1[j] += t1[j]; }
       cnt += tc;
     )
@@ -494,7 +408,7 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
   __syncthreads();
 #pragma unroll
   for (int u = 0; u < UH; ++u) dma_item(cur, u, 0);
-  r_wait_vm0();
+  wait_vm<0>();
   __syncthreads();
   if (TR) {
 #pragma unroll
@@ -502,7 +416,7 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
     __syncthreads();
   }
 
-  r_f32x4 acc[8];
+  f32x4 acc[8];
   const int n_my = (t_end - t_begin) * NC;              // units
   for (int t = 0; t < n_my; ++t) {
     const unsigned buf = (unsigned)(t & 1) * HBUF, obuf = HBUF - buf;
@@ -516,7 +430,7 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
     nx.cc = more ? nxt.cc : cur.cc;
     if (first_cc) {
 #pragma unroll
-      for (int nt = 0; nt < 8; ++nt) acc[nt] = r_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int nt = 0; nt < 8; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     const unsigned char* const w_next = w_lane + (size_t)nx.cc * 27u * w_tap;
     // (B) 9 (kh, kw) steps x HP patches: the TD+2 plane fragments of a patch stream through a ring of 5 registers,
@@ -546,7 +460,7 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
           if (TR && s >= 9 - FS) {
             const int k = s - (9 - FS);                      // 0 .. FS-1: transforms items 2k, 2k+1
             // own pieces younger than item 2k+1, plus (streamed weights) the 3 fragment loads of each step since
-            wait_vm((UH - 2 * k - 2 > 0 ? UH - 2 * k - 2 : 0) + (stream_w ? 3 * (9 - FS) : 0));
+            wait_vm_rt((UH - 2 * k - 2 > 0 ? UH - 2 * k - 2 : 0) + (stream_w ? 3 * (9 - FS) : 0));
             tr_xform(nx, 2 * k, obuf);
             if (2 * k + 1 < UH) tr_xform(nx, 2 * k + 1, obuf);
           }
@@ -559,7 +473,7 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
             // read RING-1 entries ahead; the fences keep the compiler from sinking the read next to its use (it then
             // waits a full LDS round trip every third MFMA: measured 57 % of the MFMA rate)
             if (e + RING - 1 < SEQ && !(R_DBG & 128)) xr[(e + RING - 1) % RING] = *(const u32x4*)(smem + frag_addr(e + RING - 1));
-            R_SCHED_FENCE();
+            CBIM_SCHED_FENCE();
 #pragma unroll
             for (int kd = 0; kd < 3; ++kd) {
               const int pl = i - kd;
@@ -567,7 +481,7 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
                 acc[hp * TD + pl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[(kd * 3 + kh) * 3 + kw]),
                                                                             __builtin_bit_cast(bf16x8, xr[e % RING]), acc[hp * TD + pl], 0, 0, 0);
             }
-            R_SCHED_FENCE();
+            CBIM_SCHED_FENCE();
           }
         }
         // the three fragments of this (kh, kw) are dead until step s of the next unit: reload them for it now
@@ -588,17 +502,17 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
     unsigned char* y_tile = (unsigned char*)p.y + orow * (long long)y_sb;
     const unsigned char* res_tile = (const unsigned char*)p.res + orow * (long long)res_sb;
     const unsigned char* mx_tile = (const unsigned char*)p.mx + orow * (long long)mx_sb;
-    const unsigned plane2 = 2u * r_mul24((unsigned)p.Ho, (unsigned)p.Wo);
+    const unsigned plane2 = 2u * umul24((unsigned)p.Ho, (unsigned)p.Wo);
     const unsigned cb = (unsigned)(oc * 4 + cidx) * 16u;
     // after the exchange this lane owns, for pair pr = (hp, pp): chunk cidx of voxel (2pp + (lq&1), th(hp), tw)
     constexpr int NPAIR = 4;                               // 8 n-tiles
     // (the offsets below depend on the lane only: laundering the lane's plane bit keeps the compiler from hoisting the
     //  four of them — and the 64-bit addresses built on them — out of the tile loop, where they were spilled to scratch
     //  and reloaded in every epilogue: 12-17 spilled VGPRs in the masked multi-chunk instantiations)
-    const unsigned lq1 = r_launder((unsigned)(lq & 1));
+    const unsigned lq1 = launder((unsigned)(lq & 1));
     auto pair_rel = [&](int pr) -> unsigned {
       const int hp = pr / (TD / 2), pp = pr % (TD / 2);
-      return r_mul24(r_mul24(lq1, (unsigned)p.Ho) + (unsigned)thp[hp], (unsigned)p.Wo) + (unsigned)tw + (unsigned)pp * plane2;
+      return umul24(umul24(lq1, (unsigned)p.Ho) + (unsigned)thp[hp], (unsigned)p.Wo) + (unsigned)tw + (unsigned)pp * plane2;
     };
     auto pair_in = [&](int pr) -> bool {
       const int hp = pr / (TD / 2), pp = pr % (TD / 2);
@@ -613,8 +527,8 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
         const bool in = pair_in(pr) && c_ok && !(R_DBG & (4 | 8));
         const unsigned rel = pair_rel(pr);
         if (in) {
-          if (MX) rq[pr] = *(const u32x4*)(mx_tile + (r_mul24(rel, mx_sb) + cb));
-          else if (p.res) rq[pr] = *(const u32x4*)(res_tile + (r_mul24(rel, res_sb) + cb));
+          if (MX) rq[pr] = *(const u32x4*)(mx_tile + (umul24(rel, mx_sb) + cb));
+          else if (p.res) rq[pr] = *(const u32x4*)(res_tile + (umul24(rel, res_sb) + cb));
         }
       }
       load_mstats(cur.n);
@@ -623,8 +537,8 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
     //     LDS stores drained)
     // own LDS-DMA pieces landed.  Streamed weights: the fragment loads issued after the last piece (steps FS-1 .. 8) may
     // stay in flight (vector-memory operations complete in order)
-    if (stream_w) wait_vm(3 * (10 - (UH + 1) / 2));
-    else r_wait_vm0();
+    if (stream_w) wait_vm_rt(3 * (10 - (UH + 1) / 2));
+    else wait_vm<0>();
     __syncthreads();
     // (C) epilogue of this tile — no barrier inside (except at an image change); its stores drain under the next
     //     tile's MFMAs
@@ -652,27 +566,26 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float a = acc[2 * pr][r], b = acc[2 * pr + 1][r];
-          r_swap16(a, b);
+          swap16(a, b);
           v[r] = a;
           v[4 + r] = b;
         }
         // packed f32 pairs from here on (v_pk_add / v_pk_mul / v_pk_fma); lanes outside the tensor or beyond Cout
         // contribute with weight 0 instead of branching
-        typedef float f2_t __attribute__((ext_vector_type(2)));
         const float live = (in && c_ok) ? 1.f : 0.f;
-        const f2_t live2 = {live, live};
+        const f32x2 live2 = {live, live};
         const unsigned rw[4] = {rq[pr].x, rq[pr].y, rq[pr].z, rq[pr].w};
         if (MX && mask_is_act) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const f2_t a = {__uint_as_float(rw[j] << 16), __uint_as_float(rw[j] & 0xffff0000u)};
-            f2_t g;
+            const f32x2 a = {__uint_as_float(rw[j] << 16), __uint_as_float(rw[j] & 0xffff0000u)};
+            f32x2 g;
             g.x = (rw[j] & 0xffffu) != 0u ? v[2 * j] : 0.f;
             g.y = (rw[j] >> 16) != 0u ? v[2 * j + 1] : 0.f;
             v[2 * j] = g.x;
             v[2 * j + 1] = g.y;
-            const f2_t gl = g * live2;
-            f2_t a0 = {S0[2 * j], S0[2 * j + 1]}, a1 = {S1[2 * j], S1[2 * j + 1]};
+            const f32x2 gl = g * live2;
+            f32x2 a0 = {S0[2 * j], S0[2 * j + 1]}, a1 = {S1[2 * j], S1[2 * j + 1]};
             a0 = a0 + gl;
             a1 = __builtin_elementwise_fma(gl, a, a1);
             S0[2 * j] = a0.x; S0[2 * j + 1] = a0.y; S1[2 * j] = a1.x; S1[2 * j + 1] = a1.y;
@@ -682,16 +595,16 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const f32x4 q4 = *(const f32x4*)(ms + 4 * j);   // (mean, rstd) of channels 2j, 2j+1
-            const f2_t x = {__uint_as_float(rw[j] << 16), __uint_as_float(rw[j] & 0xffff0000u)};
-            const f2_t m = {q4.x, q4.z}, r = {q4.y, q4.w};
-            const f2_t xh = (x - m) * r;
-            f2_t g;
+            const f32x2 x = {__uint_as_float(rw[j] << 16), __uint_as_float(rw[j] & 0xffff0000u)};
+            const f32x2 m = {q4.x, q4.z}, r = {q4.y, q4.w};
+            const f32x2 xh = (x - m) * r;
+            f32x2 g;
             if (ACT == CBIM_ACT_RELU) { g.x = xh.x > 0.f ? v[2 * j] : 0.f; g.y = xh.y > 0.f ? v[2 * j + 1] : 0.f; }
             else { g.x = v[2 * j]; g.y = v[2 * j + 1]; }
             v[2 * j] = g.x;
             v[2 * j + 1] = g.y;
-            const f2_t gl = g * live2;
-            f2_t a0 = {S0[2 * j], S0[2 * j + 1]}, a1 = {S1[2 * j], S1[2 * j + 1]};
+            const f32x2 gl = g * live2;
+            f32x2 a0 = {S0[2 * j], S0[2 * j + 1]}, a1 = {S1[2 * j], S1[2 * j + 1]};
             a0 = a0 + gl;
             a1 = __builtin_elementwise_fma(gl, xh, a1);
             S0[2 * j] = a0.x; S0[2 * j + 1] = a0.y; S1[2 * j] = a1.x; S1[2 * j + 1] = a1.y;
@@ -710,16 +623,16 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-              const f2_t x = {v[2 * j], v[2 * j + 1]}, hs = {SH[MX ? 0 : 2 * j], SH[MX ? 0 : 2 * j + 1]};
-              const f2_t d = (x - hs) * live2;
-              f2_t a0 = {S0[2 * j], S0[2 * j + 1]}, a1 = {S1[2 * j], S1[2 * j + 1]};
+              const f32x2 x = {v[2 * j], v[2 * j + 1]}, hs = {SH[MX ? 0 : 2 * j], SH[MX ? 0 : 2 * j + 1]};
+              const f32x2 d = (x - hs) * live2;
+              f32x2 a0 = {S0[2 * j], S0[2 * j + 1]}, a1 = {S1[2 * j], S1[2 * j + 1]};
               a0 = a0 + d;
               a1 = __builtin_elementwise_fma(d, d, a1);
               S0[2 * j] = a0.x; S0[2 * j + 1] = a0.y; S1[2 * j] = a1.x; S1[2 * j + 1] = a1.y;
             }
           }
         }
-        if (in && c_ok && !(R_DBG & 16)) *(u32x4*)(y_tile + (r_mul24(rel, y_sb) + cb)) = Elem<bf16_tag>::pack(v);
+        if (in && c_ok && !(R_DBG & 16)) *(u32x4*)(y_tile + (umul24(rel, y_sb) + cb)) = Elem<bf16_tag>::pack(v);
         CNT += live;
       }
       if (LS && want_part && !(R_DBG & 32)) tile_stats(l0, l1, lsh, lcnt);

@@ -14,7 +14,7 @@
 //   * halo pieces are PLANE-major: piece j of halo plane p = rows 16 j .. 16 j + 15 of the plane's 100 (the seventh piece
 //     re-covers rows 84..99), wave w fetches piece w of every plane.  A lane's (h, w) position inside the box, its swizzled
 //     16-byte slot and so its source offset are then the SAME for all ten pieces: one VGPR, computed once per kernel;
-//   * the pieces are `buffer_load_dwordx4 ... offen lds`: the tile / plane origin travels in the scalar offset, the lane
+//   * the pieces go through a buffer descriptor (lds_dma16_buf): the tile / plane origin travels in the scalar offset, the lane
 //     offset in the vector offset, and zero padding is the buffer range check — a lane outside the tensor gets the offset
 //     0x80000000 (out of range: zeros land in LDS, checked on the hardware), a plane outside the tensor a descriptor with
 //     num_records = 0.  Per tile: two compares and a select; per piece: three scalar instructions and the load.  No zero page,
@@ -27,6 +27,7 @@
 // partial-record format as conv_r32.hip / conv_igemm.hip.  Replaces aten::convolution / convolution_backward(input) of
 // nn.Conv3d in ConvNormAct (/root/reference/model/dim3/conv_layers.py:29-38, 48-49: zero padding after the activation).
 #include "cbim_common.h"
+#include "gfx950_prims.h"
 #include "conv_r32.h"
 #include <stdlib.h>
 #include <stdio.h>
@@ -40,87 +41,6 @@ static constexpr unsigned W_RED = W_SHF + 512u;          // wave records [8][16 
 static constexpr unsigned W_SMEM = W_RED + 1536u;
 static_assert(W_SMEM <= 160 * 1024, "LDS");
 static constexpr unsigned W_OOB = 0x80000000u;           // vector offset of a lane outside the tensor (num_records = 2^31)
-
-typedef __attribute__((ext_vector_type(4))) float w_f32x4;
-typedef __attribute__((ext_vector_type(4))) int w_i32x4;
-
-#ifdef CBIM_EMU
-#define W_SCHED_FENCE() ((void)0)
-#define W_DYN_SMEM(name) unsigned char* name = cbim_emu::dyn_smem()
-#else
-#define W_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define W_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
-#endif
-
-// one 1 KiB LDS-DMA piece: lane l copies the 16 bytes at base + soff + voff (zeros when soff + voff + 16 > nrec) to LDS
-// byte lds + 16 l.  M0 (the LDS base of the instruction) is saved and restored inside the statement.
-__device__ __forceinline__ void w_dma16(unsigned voff, unsigned long long base, unsigned nrec, unsigned soff, unsigned char* smem,
-                                        unsigned lds_base, unsigned lds_off) {
-#ifdef CBIM_EMU
-  (void)lds_base;
-  emu_buffer_load_lds16((const unsigned char*)base, nrec, voff, soff, smem + lds_off);
-#else
-  (void)smem;
-  w_i32x4 rs = {(int)(unsigned)base, (int)((unsigned)(base >> 32) & 0xffffu), (int)nrec, 0x00020000};
-  rs.x = __builtin_amdgcn_readfirstlane(rs.x); rs.y = __builtin_amdgcn_readfirstlane(rs.y);
-  rs.z = __builtin_amdgcn_readfirstlane(rs.z);
-  const unsigned a = __builtin_amdgcn_readfirstlane(lds_base + lds_off), so = __builtin_amdgcn_readfirstlane(soff);
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "s"(a), "v"(voff), "s"(rs), "s"(so) : "memory");
-#endif
-}
-template <int N>
-__device__ __forceinline__ void w_wait_vm() {
-#ifndef CBIM_EMU
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-#endif
-}
-__device__ __forceinline__ unsigned w_mul24(unsigned a, unsigned b) {
-#ifdef CBIM_EMU
-  return a * b;
-#else
-  return __umul24(a, b);
-#endif
-}
-__device__ __forceinline__ unsigned w_swz(unsigned hh) { return (hh & 1u) << 1; }   // (conv_r32.hip r_swz)
-template <int MSK>
-__device__ __forceinline__ float w_bfly(float v) {                                  // (conv_r32.hip r_bfly)
-#ifdef CBIM_EMU
-  return __shfl_xor(v, MSK, 64);
-#else
-  if (MSK == 16) return __shfl_xor(v, 16, 64);
-  constexpr int ctrl = MSK == 1 ? 0xB1 : MSK == 2 ? 0x4E : MSK == 4 ? 0x141 : 0x140;
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, false));
-#endif
-}
-__device__ __forceinline__ void w_swap16(float& a, float& b) {                      // (conv_r32.hip r_swap16)
-#ifdef CBIM_EMU
-  struct P { float a, b; } mine = {a, b};
-  const P* buf = (const P*)cbim_emu::wave_exchange(&mine, sizeof(P));
-  const int l = CBIM_EMU_LANE_ID();
-  if (l & 16) a = buf[l - 16].b;
-  else b = buf[l + 16].a;
-#else
-  typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-  u2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r.x);
-  b = __uint_as_float(r.y);
-#endif
-}
-__device__ __forceinline__ unsigned w_launder(unsigned v) {     // keeps a loop-invariant value (and what is derived from it) inside the loop
-#ifndef CBIM_EMU
-  asm volatile("" : "+v"(v));
-#endif
-  return v;
-}
-__device__ __forceinline__ int w_uniform(int v) {
-#ifdef CBIM_EMU
-  return v;
-#else
-  return __builtin_amdgcn_readfirstlane(v);
-#endif
-}
 
 // cycle profile of the phases of a unit (make EXTRA=-DCBIM_RW_PROF; tools/r04/run_prof.sh): s_memtime stamps of every wave of
 // workgroup 0, summed over its units, printed per launch by the launcher
@@ -150,7 +70,7 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
   static_assert(!SK || (MC && !MX), "split-K: forward-style epilogue over several Cin chunks");
   static_assert(!LR || MX, "the leaky mask belongs to the dgrad epilogue");
   constexpr int NT = 512, NW = 8, NTL = 8 * HP, NPAIR = 4 * HP, CB = CBW;
-  const int tid = threadIdx.x, wave = w_uniform(tid >> 6), lane = tid & 63, lv = lane & 15, lq = lane >> 4;
+  const int tid = threadIdx.x, wave = uniform(tid >> 6), lane = tid & 63, lv = lane & 15, lq = lane >> 4;
   const int tiles_per_n = p.tiles_d * p.tiles_h * p.tiles_w;
   const int n_tiles = p.N * tiles_per_n;
   const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
@@ -178,7 +98,7 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
     thp[hp] = 2 * (hp0 + hp) + (lv >> 3);
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh)
-      fb[hp][kh] = (unsigned)((thp[hp] + kh) * 10 + tw) * 64u + (((unsigned)lq ^ w_swz((unsigned)(thp[hp] + kh))) << 4);
+      fb[hp][kh] = (unsigned)((thp[hp] + kh) * 10 + tw) * 64u + (((unsigned)lq ^ halo_swz((unsigned)(thp[hp] + kh))) << 4);
   }
 
   // ---- this lane's halo item: row r = r0 + (lane >> 2) of a plane, physical slot lane & 3 ------------------------------
@@ -186,10 +106,10 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
   const int r0 = pj < 6 ? 16 * pj : 84;
   const unsigned hrow = (unsigned)r0 + ((unsigned)lane >> 2);
   const unsigned hh = (hrow * 205u) >> 11, hw = hrow - hh * 10u;           // hrow / 10, hrow % 10 (hrow < 100)
-  const unsigned slot_src = (((unsigned)lane & 3u) ^ w_swz(hh)) << 4;
-  const unsigned rows_hw = w_mul24(hh, (unsigned)p.Wi) + hw;
-  const unsigned lane_off = w_mul24(rows_hw, x_sb) + slot_src;
-  const unsigned lane_off2 = MC ? w_mul24(rows_hw, x2_sb) + slot_src : 0u;
+  const unsigned slot_src = (((unsigned)lane & 3u) ^ halo_swz(hh)) << 4;
+  const unsigned rows_hw = umul24(hh, (unsigned)p.Wi) + hw;
+  const unsigned lane_off = umul24(rows_hw, x_sb) + slot_src;
+  const unsigned lane_off2 = MC ? umul24(rows_hw, x2_sb) + slot_src : 0u;
   const unsigned piece_lds = (unsigned)r0 * 64u;                           // + plane * 6400 + buffer
 
   struct TilePos { int n, td, th, tw, cc; };            // a unit: tile + Cin chunk
@@ -231,7 +151,7 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
     const int d = h.id0 + pl;
     const bool in = (unsigned)d < (unsigned)p.Di;
     const unsigned soff = in ? h.soff0 + (unsigned)d * h.plane_b : 0u;
-    w_dma16(h.voff, h.base, in ? 0x80000000u : 0u, soff, smem, lds_base, buf + (unsigned)pl * 6400u + piece_lds);
+    lds_dma16_buf(h.voff, h.base, in ? 0x80000000u : 0u, soff, smem, lds_base, buf + (unsigned)pl * 6400u + piece_lds);
   };
 
   // ---- statistics -------------------------------------------------------------------------------------------------------
@@ -263,8 +183,8 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
 #define W_ROUND(msk)                                                                                              \
     {                                                                                                             \
       float u0[8], u1[8];                                                                                         \
-      _Pragma("unroll") for (int j = 0; j < 8; ++j) { u0[j] = w_bfly<msk>(t0[j]); u1[j] = w_bfly<msk>(t1[j]); }    \
-      const float uc = w_bfly<msk>(tc);                                                                           \
+      _Pragma("unroll") for (int j = 0; j < 8; ++j) { u0[j] = dpp_bfly<msk>(t0[j]); u1[j] = dpp_bfly<msk>(t1[j]); }  \
+      const float uc = dpp_bfly<msk>(tc);                                                                         \
       _Pragma("unroll") for (int j = 0; j < 8; ++j) { t0[j] += u0[j]; t1[j] += u1[j]; }                           \
       tc += uc;                                                                                                   \
     }
@@ -328,11 +248,11 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
 #pragma unroll
     for (int tp = 0; tp < 27; ++tp) asm volatile("" : "+v"(wf[tp]));
 #endif
-    w_wait_vm<0>();
+    wait_vm<0>();
     __syncthreads();
   }
 
-  w_f32x4 acc[NTL];
+  f32x4 acc[NTL];
   const int n_my = (t_end - t_begin) * (cc_hi - cc_lo);  // units
 #ifdef CBIM_RW_PROF
   unsigned long long prof_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prof_last = __builtin_readcyclecounter();
@@ -347,7 +267,7 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
     const Halo hn = halo_of(nx);
     if (first_cc) {
 #pragma unroll
-      for (int nt = 0; nt < NTL; ++nt) acc[nt] = w_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int nt = 0; nt < NTL; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     // ---- epilogue addressing of this tile (used by the operand requests inside the MFMA loop and by the epilogue) ----------
     const int n = cur.n;
@@ -361,13 +281,13 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
     // pair pr = (hp, pp): after the exchange this lane owns chunk cidx of voxel (plane 2 pp + (lq & 1), thp[hp], tw)
     // (the offsets below depend on the lane only: laundering the lane index keeps the compiler from hoisting them — and the
     //  64-bit addresses built on them — out of the unit loop, where they would be spilled and reloaded in every epilogue)
-    const unsigned lane_l = w_launder((unsigned)lane);
+    const unsigned lane_l = launder((unsigned)lane);
     const unsigned e_lq1 = (lane_l >> 4) & 1u, e_tw = lane_l & 7u, e_h8 = (lane_l >> 3) & 1u;
     u32x4* const cell = (u32x4*)(smem + W_ACC) + (wave * 64 + lane_l);                        // (as cell0 / shf0 above)
     const float* const shf = (const float*)(smem + W_SHF) + (wave * 2 + (lane_l >> 5)) * 8;
     auto pair_rows = [&](int pr) -> unsigned {
       const int hp = pr / 4, pp = pr % 4;
-      return w_mul24(w_mul24((unsigned)(2 * pp) + e_lq1, (unsigned)p.Ho) + (unsigned)(2 * (hp0 + hp)) + e_h8, (unsigned)p.Wo) + e_tw;
+      return umul24(umul24((unsigned)(2 * pp) + e_lq1, (unsigned)p.Ho) + (unsigned)(2 * (hp0 + hp)) + e_h8, (unsigned)p.Wo) + e_tw;
     };
     auto pair_in = [&](int pr) -> bool {
       const int hp = pr / 4, pp = pr % 4;
@@ -382,7 +302,7 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
     constexpr int RQ_STEP = 6;
     u32x4 rq[QD];
     auto request = [&](int pr) -> u32x4 {
-      const unsigned off = pair_in(pr) ? w_mul24(pair_rows(pr), q_sb) + cbyte : 0u;
+      const unsigned off = pair_in(pr) ? umul24(pair_rows(pr), q_sb) + cbyte : 0u;
       return *(const u32x4*)(q_tile + off);
     };
     const unsigned char* const w_next = w_lane + (size_t)nx.cc * 27u * w_tap;
@@ -416,7 +336,7 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
           for (int i = 0; i < PLN; ++i) {
             const int e = (s * HP + hp) * PLN + i;
             if (e + RING - 1 < SEQ) xr[(e + RING - 1) % RING] = *(const u32x4*)(smem + frag_addr(e + RING - 1));
-            W_SCHED_FENCE();
+            CBIM_SCHED_FENCE();
 #pragma unroll
             for (int kd = 0; kd < 3; ++kd) {
               const int pl = i - kd;
@@ -424,7 +344,7 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
                 acc[hp * 8 + pl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[(kd * 3 + kh) * 3 + kw]),
                                                                            __builtin_bit_cast(bf16x8, xr[e % RING]), acc[hp * 8 + pl], 0, 0, 0);
             }
-            W_SCHED_FENCE();
+            CBIM_SCHED_FENCE();
           }
         }
         // the three fragments of this (kh, kw) are dead until step s of the next unit: reload them for it now
@@ -439,9 +359,9 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
     //      memory operations complete in order, so the 15 weight-fragment loads / the QD operand requests issued after the last
     //      piece may stay in flight)
     W_STAMP(1);                                          // MFMA loop (+ piece issue, weight reloads, operand requests)
-    if (MC) w_wait_vm<15>();
-    else if (last_cc && has_q) w_wait_vm<QD>();          // (the QD operand requests are the youngest operations)
-    else w_wait_vm<0>();
+    if (MC) wait_vm<15>();
+    else if (last_cc && has_q) wait_vm<QD>();          // (the QD operand requests are the youngest operations)
+    else wait_vm<0>();
     W_STAMP(3);                                          // own pieces landed
     __syncthreads();
     W_STAMP(4);                                          // barrier
@@ -455,7 +375,7 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float a = acc[2 * pr][r], b = acc[2 * pr + 1][r];
-          w_swap16(a, b);
+          swap16(a, b);
           v[r] = a;
           v[4 + r] = b;
         }
@@ -468,10 +388,9 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
     }
     if (!SK && last_cc) {
       if (want_part && n != run_n) { flush_stats(run_n); run_n = n; }
-      typedef float f2_t __attribute__((ext_vector_type(2)));
-      f2_t l0[4], l1[4];
+      f32x2 l0[4], l1[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { l0[j] = f2_t{0.f, 0.f}; l1[j] = f2_t{0.f, 0.f}; }
+      for (int j = 0; j < 4; ++j) { l0[j] = f32x2{0.f, 0.f}; l1[j] = f32x2{0.f, 0.f}; }
 #pragma unroll
       for (int pr = 0; pr < NPAIR; ++pr) {
         const bool in = pair_in(pr);
@@ -480,7 +399,7 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float a = acc[2 * pr][r], b = acc[2 * pr + 1][r];
-          w_swap16(a, b);
+          swap16(a, b);
           v[r] = a;
           v[4 + r] = b;
         }
@@ -490,13 +409,13 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
           if (pr + QD < NPAIR) rq[pr % QD] = request(pr + QD);      // next request into the slot just read
         }
         const float live = in ? 1.f : 0.f;
-        const f2_t live2 = {live, live};
+        const f32x2 live2 = {live, live};
         const unsigned rw[4] = {q.x, q.y, q.z, q.w};
         if (MX) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            f2_t a = {__uint_as_float(rw[j] << 16), __uint_as_float(rw[j] & 0xffff0000u)};
-            f2_t g;
+            f32x2 a = {__uint_as_float(rw[j] << 16), __uint_as_float(rw[j] & 0xffff0000u)};
+            f32x2 g;
             if (LR) {
               // a = lrelu(xh): a > 0 passes the gradient, anything else (negative, -0, 0) takes the slope — torch's
               // leaky_relu_backward tests x > 0; xh is recovered from a for the InstanceNorm-backward sum
@@ -511,7 +430,7 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
             }
             v[2 * j] = g.x;
             v[2 * j + 1] = g.y;
-            const f2_t gl = g * live2;
+            const f32x2 gl = g * live2;
             l0[j] = l0[j] + gl;
             l1[j] = __builtin_elementwise_fma(gl, a, l1[j]);
 #ifndef CBIM_EMU
@@ -541,13 +460,13 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
 #endif
             }
             // (the shift is read per pair — two broadcast LDS reads — instead of living in 8 registers through the epilogue)
-            const float* const shp = shf + w_launder(0u);   // (a fresh address per pair: the two reads are not merged into 8 live registers)
+            const float* const shp = shf + launder(0u);   // (a fresh address per pair: the two reads are not merged into 8 live registers)
             const f32x4 sa = *(const f32x4*)shp, sb4 = *(const f32x4*)(shp + 4);
-            const f2_t sh2[4] = {f2_t{sa.x, sa.y}, f2_t{sa.z, sa.w}, f2_t{sb4.x, sb4.y}, f2_t{sb4.z, sb4.w}};
+            const f32x2 sh2[4] = {f32x2{sa.x, sa.y}, f32x2{sa.z, sa.w}, f32x2{sb4.x, sb4.y}, f32x2{sb4.z, sb4.w}};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-              const f2_t x = {v[2 * j], v[2 * j + 1]};
-              const f2_t d = (x - sh2[j]) * live2;
+              const f32x2 x = {v[2 * j], v[2 * j + 1]};
+              const f32x2 d = (x - sh2[j]) * live2;
               l0[j] = l0[j] + d;
               l1[j] = __builtin_elementwise_fma(d, d, l1[j]);
 #ifndef CBIM_EMU
@@ -556,7 +475,7 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
             }
           }
         }
-        if (in) *(u32x4*)(y_tile + (w_mul24(rows, y_sb) + cbyte)) = Elem<bf16_tag>::pack(v);
+        if (in) *(u32x4*)(y_tile + (umul24(rows, y_sb) + cbyte)) = Elem<bf16_tag>::pack(v);
         cnt += live;
       }
       if (want_part) {                                   // this tile's sums into the lane's cells
@@ -589,13 +508,13 @@ __device__ __forceinline__ void rw_body(const R32Params& p, unsigned char* const
 
 template <bool MX, int HP, bool MC, bool SK = false>
 __global__ void __launch_bounds__(512, 1) k_conv3_rw(R32Params p) {
-  W_DYN_SMEM(smem);
+  CBIM_DYN_SMEM(smem);
 #ifdef CBIM_EMU
   const unsigned lds_base = 0;
 #else
   const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
 #endif
-  const int wave = w_uniform((int)threadIdx.x >> 6);
+  const int wave = uniform((int)threadIdx.x >> 6);
   rw_body<MX, HP, MC, SK, 32 * HP, false>(p, smem, lds_base, HP == 1 ? (wave & 1) : (wave & 3), HP == 1 ? (wave >> 1) : 2 * (wave >> 2), wave);
 }
 
@@ -608,13 +527,13 @@ __global__ void __launch_bounds__(512, 1) k_conv3_rw(R32Params p) {
 // The halo pieces go to the light waves first (pieces 0..3 on waves 4..7, 4..6 on waves 0..2).
 template <bool MX, bool LR>
 __global__ void __launch_bounds__(512, 1) k_conv3_rw48(R32Params p) {
-  W_DYN_SMEM(smem);
+  CBIM_DYN_SMEM(smem);
 #ifdef CBIM_EMU
   const unsigned lds_base = 0;
 #else
   const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
 #endif
-  const int wave = w_uniform((int)threadIdx.x >> 6);
+  const int wave = uniform((int)threadIdx.x >> 6);
   if (wave < 4) rw_body<MX, 2, true, false, 48, LR>(p, smem, lds_base, wave >> 1, 2 * (wave & 1), wave + 4);
   else rw_body<MX, 1, true, false, 48, LR>(p, smem, lds_base, 2, wave - 4, wave - 4);
 }

@@ -18,6 +18,7 @@
 // Replaces aten::convolution_backward(weight) for nn.Conv3d in ConvNormAct
 // (/root/reference/model/dim3/conv_layers.py:29-38).
 #include "cbim_common.h"
+#include "gfx950_prims.h"
 #include <stdlib.h>
 #include "conv_wgrad_r32.h"
 #include "conv_r32.h"
@@ -40,51 +41,6 @@ struct WgradParams {
   unsigned long long* prof;        // tools/ only: per-wave cycle totals of the tile-loop phases
 #endif
 };
-
-#ifdef CBIM_EMU
-#define CBIM_DYN_SMEM(name) unsigned char* name = cbim_emu::dyn_smem()
-#else
-#define CBIM_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
-#endif
-
-// 4 consecutive-voxel bf16 of one channel via the LDS transpose read (per-lane address of 4 bf16).
-__device__ __forceinline__ u32x2 lds_tr16_b64(const unsigned char* p) {
-#ifdef CBIM_EMU
-  unsigned short o[4];
-  emu_ds_read_tr16_b64(p, o);
-  u32x2 r;
-  r.x = (unsigned)o[0] | ((unsigned)o[1] << 16);
-  r.y = (unsigned)o[2] | ((unsigned)o[3] << 16);
-  return r;
-#else
-  typedef __attribute__((ext_vector_type(4))) short s16x4;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
-  return __builtin_bit_cast(u32x2, v);
-#endif
-}
-
-// 24-bit multiply-add (full rate): row and byte offsets inside one tile box
-__device__ __forceinline__ unsigned wmad24(unsigned a, unsigned b, unsigned c) {
-#ifdef CBIM_EMU
-  return a * b + c;
-#else
-  return __umul24(a, b) + c;
-#endif
-}
-
-#ifdef CBIM_EMU
-#define WG_SCHED_FENCE() ((void)0)
-#else
-#define WG_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
-
-template <int ACT> __device__ __forceinline__ float wg_actf(float x, int rt) {
-  if (ACT == CBIM_ACT_RELU) return x > 0.f ? x : 0.f;
-  if (ACT == CBIM_ACT_LRELU) return x > 0.f ? x : 0.01f * x;
-  if (ACT == CBIM_ACT_NONE) return x;
-  return act_fwd(x, rt);
-}
 
 template <int TPW> struct WFrag { u32x4 a; u32x4 b[TPW]; };   // bf16: 8 voxels x 1 channel per operand
 template <int TPW> struct WFragF { float a; float b[TPW]; };  // f32 : 1 voxel per operand
@@ -150,7 +106,7 @@ __global__ void __launch_bounds__(NT, 2) k_conv_wgrad(WgradParams p) {
 
   auto halo_row = [&](int m) -> unsigned {   // LDS row (bytes) of tile voxel m at tap (0,0,0)
     unsigned tw = m & 7, th = (m >> 3) & (p.tH - 1), td = m >> (3 + p.lgH);
-    return wmad24(wmad24(td, (unsigned)p.hH, th), (unsigned)p.hW, tw) * ROWB;
+    return umad24(umad24(td, (unsigned)p.hH, th), (unsigned)p.hW, tw) * ROWB;
   };
   auto fetch16 = [&](WFrag<TPW>& f, int ks) {
     int m0 = ks * 16 + mq, m1 = m0 + 4;
@@ -225,7 +181,7 @@ __global__ void __launch_bounds__(NT, 2) k_conv_wgrad(WgradParams p) {
       const unsigned tw = m & 7, th = (m >> 3) & (p.tH - 1), td = m >> (3 + p.lgH);
       vd[u] = u32x4{0u, 0u, 0u, 0u};
       if (item < d_items && co0 < p.Cout && od0 + (int)td < p.Do && oh0 + (int)th < p.Ho && ow0 + (int)tw < p.Wo)
-        vd[u] = *(const u32x4*)(dy_tile + wmad24(wmad24(wmad24(td, (unsigned)p.Ho, th), (unsigned)p.Wo, tw), dy_sb, dy_cb));
+        vd[u] = *(const u32x4*)(dy_tile + umad24(umad24(umad24(td, (unsigned)p.Ho, th), (unsigned)p.Wo, tw), dy_sb, dy_cb));
     }
 #pragma unroll
     for (int u = 0; u < UA; ++u) {
@@ -238,7 +194,7 @@ __global__ void __launch_bounds__(NT, 2) k_conv_wgrad(WgradParams p) {
       const bool ld = item < a_items && ci0 < p.Cin && (unsigned)(id0 + (int)hd) < (unsigned)p.Di &&
                       (unsigned)(ih0 + (int)hh) < (unsigned)p.Hi && (unsigned)(iw0 + (int)hw) < (unsigned)p.Wi;
       va[u] = u32x4{0u, 0u, 0u, 0u};
-      if (ld) va[u] = *(const u32x4*)(x_tile + wmad24(wmad24(wmad24(hd, (unsigned)p.Hi, hh), (unsigned)p.Wi, hw), x_sb, x_cb));
+      if (ld) va[u] = *(const u32x4*)(x_tile + umad24(umad24(umad24(hd, (unsigned)p.Hi, hh), (unsigned)p.Wi, hw), x_sb, x_cb));
       lda |= (ld ? 1u : 0u) << u;
     }
 #pragma unroll
@@ -251,7 +207,7 @@ __global__ void __launch_bounds__(NT, 2) k_conv_wgrad(WgradParams p) {
       float f[CPC];
       Elem<T>::unpack(w, f);
 #pragma unroll
-      for (int j = 0; j < CPC; ++j) f[j] = wg_actf<ACT>((f[j] - mean[j]) * rstd[j], p.act);
+      for (int j = 0; j < CPC; ++j) f[j] = act_fwd_t<ACT>((f[j] - mean[j]) * rstd[j], p.act);
       return Elem<T>::pack(f);
     };
 #pragma unroll
@@ -274,7 +230,7 @@ __global__ void __launch_bounds__(NT, 2) k_conv_wgrad(WgradParams p) {
                       (unsigned)(iw0 + (int)hw) < (unsigned)p.Wi;
       u32x4 w = u32x4{0u, 0u, 0u, 0u};
       if (ld) {
-        w = *(const u32x4*)(x_tile + wmad24(wmad24(wmad24(hd, (unsigned)p.Hi, hh), (unsigned)p.Wi, hw), x_sb, x_cb));
+        w = *(const u32x4*)(x_tile + umad24(umad24(umad24(hd, (unsigned)p.Hi, hh), (unsigned)p.Wi, hw), x_sb, x_cb));
         if (p.in_stats) w = xform(w);
       }
       *(u32x4*)(smem + aL + (unsigned)base * 16) = w;
@@ -309,13 +265,13 @@ __global__ void __launch_bounds__(NT, 2) k_conv_wgrad(WgradParams p) {
 #pragma unroll
       for (int ks = 0; ks < 16; ks += 2) {
         fetchk(f1, ks + 1);
-        WG_SCHED_FENCE();
+        CBIM_SCHED_FENCE();
         mma16(f0);
-        WG_SCHED_FENCE();
+        CBIM_SCHED_FENCE();
         if (ks + 2 < 16) fetchk(f0, ks + 2);
-        WG_SCHED_FENCE();
+        CBIM_SCHED_FENCE();
         mma16(f1);
-        WG_SCHED_FENCE();
+        CBIM_SCHED_FENCE();
       }
     } else if (IS_BF16) {
       // a single tap (1x1x1 convs): the 4 waves split the voxel steps instead of repeating the tap, each writes

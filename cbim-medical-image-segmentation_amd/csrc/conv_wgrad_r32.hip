@@ -10,7 +10,7 @@
 // transpose (16 ds_read_b64_tr_b16 per 7 MFMAs): three rewrites of the staging left the tile time where it was
 // (DESIGN.md "measured and rejected").  The shape of the work is what changes here:
 //   * persistent 512-thread workgroup per CU on 8x8x8 tiles; the 10x10x10 input halo is DOUBLE buffered in LDS and
-//     arrives by LDS-DMA (global_load_lds_dwordx4: no registers, no vector ALU, one barrier per tile) — possible
+//     arrives by LDS-DMA (lds_dma16_buf: no registers, no vector ALU, one barrier per tile) — possible
 //     because the input needs no transform any more;
 //   * the 27 tap accumulators of a (16 co x 16 ci) quadrant live in registers for the whole strip of tiles
 //     (27 x 4 VGPRs = the register image of conv_r32's weight fragments); a wave = (quadrant, half of the tile's rows);
@@ -26,6 +26,7 @@
 // Replaces aten::convolution_backward(weight) for nn.Conv3d in ConvNormAct
 // (/root/reference/model/dim3/conv_layers.py:29-38).
 #include "cbim_common.h"
+#include "gfx950_prims.h"
 #include "conv_wgrad_r32.h"
 #include <stdlib.h>
 #include <stdio.h>
@@ -71,87 +72,6 @@ struct WR32Params {
 #ifndef WR32_SETPRIO
 #define WR32_SETPRIO 0       // 1: raise the wave's priority around each MFMA group
 #endif
-#ifdef CBIM_EMU
-#define WR_SCHED_FENCE() ((void)0)
-#define WR_DYN_SMEM(name) unsigned char* name = cbim_emu::dyn_smem()
-#else
-#define WR_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define WR_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
-#endif
-
-// one 1 KiB LDS-DMA piece: lane l copies 16 bytes from its own global address to lds_wave_base + 16 l.  M0 (the LDS
-// base of the instruction) is saved and restored inside the statement, so nothing is hidden from the compiler.
-__device__ __forceinline__ void wr_dma16(const unsigned char* gsrc, unsigned char* smem, unsigned lds_base, unsigned off) {
-#ifdef CBIM_EMU
-  (void)lds_base;
-  emu_global_load_lds16(gsrc, smem + off);
-#else
-  (void)smem;
-  const unsigned a = __builtin_amdgcn_readfirstlane(lds_base + off);
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "s"(a), "v"(gsrc) : "memory");
-#endif
-}
-// the same piece through a buffer descriptor (conv_rw.hip w_dma16): lane l copies the 16 bytes at base + soff + voff, ZEROS when
-// soff + voff + 16 > nrec — zero padding is the range check (a lane outside the tensor carries voff = 0x80000000, a plane
-// outside the tensor nrec = 0), the tile / plane origin travels in the scalar offset
-typedef __attribute__((ext_vector_type(4))) int wr_i32x4;
-__device__ __forceinline__ void wr_bdma16(unsigned voff, unsigned long long base, unsigned nrec, unsigned soff, unsigned char* smem,
-                                          unsigned lds_base, unsigned off) {
-#ifdef CBIM_EMU
-  (void)lds_base;
-  emu_buffer_load_lds16((const unsigned char*)base, nrec, voff, soff, smem + off);
-#else
-  (void)smem;
-  wr_i32x4 rs = {(int)(unsigned)base, (int)((unsigned)(base >> 32) & 0xffffu), (int)nrec, 0x00020000};
-  rs.x = __builtin_amdgcn_readfirstlane(rs.x); rs.y = __builtin_amdgcn_readfirstlane(rs.y);
-  rs.z = __builtin_amdgcn_readfirstlane(rs.z);
-  const unsigned a = __builtin_amdgcn_readfirstlane(lds_base + off), so = __builtin_amdgcn_readfirstlane(soff);
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "s"(a), "v"(voff), "s"(rs), "s"(so) : "memory");
-#endif
-}
-__device__ __forceinline__ void wr_wait_vm0() {
-#ifndef CBIM_EMU
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-}
-__device__ __forceinline__ void wr_wait_lgkm0() {
-#ifndef CBIM_EMU
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-}
-__device__ __forceinline__ unsigned wr_mul24(unsigned a, unsigned b) {
-#ifdef CBIM_EMU
-  return a * b;
-#else
-  return __umul24(a, b);
-#endif
-}
-// 4 consecutive-voxel bf16 of one channel via the LDS transpose read (per-lane address of 4 bf16)
-__device__ __forceinline__ u32x2 wr_tr16_b64(const unsigned char* p) {
-#ifdef CBIM_EMU
-  unsigned short o[4];
-  emu_ds_read_tr16_b64(p, o);
-  u32x2 r;
-  r.x = (unsigned)o[0] | ((unsigned)o[1] << 16);
-  r.y = (unsigned)o[2] | ((unsigned)o[3] << 16);
-  return r;
-#else
-  typedef __attribute__((ext_vector_type(4))) short s16x4;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
-  return __builtin_bit_cast(u32x2, v);
-#endif
-}
-// XOR key of the 16-byte slot inside an LDS row, by the row's h coordinate: the four 16-lane groups of a transposed
-// read sit on four consecutive h rows (640 / 512 bytes apart = 128 / 0 modulo the 256-byte bank window); alternating
-// the 32-byte halves spreads them over all banks (same key as the conv_r32 halo)
-__device__ __forceinline__ unsigned wr_swz(unsigned h) { return (h & 1u) << 1; }
-
-typedef __attribute__((ext_vector_type(4))) float wr_f32x4;
 
 // cycle profile of the phases of a tile (make EXTRA=-DCBIM_WR32_PROF): s_memtime stamps of every wave of workgroup (0, 0),
 // summed over its tiles, printed per launch by the launcher
@@ -166,7 +86,7 @@ template <int WV, int DBG = 0>
 __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
   constexpr int WR_NT = WV * 64;
   constexpr int NCH = WV == 8 ? 1 : 2;                                // co halves per wave
-  WR_DYN_SMEM(smem);
+  CBIM_DYN_SMEM(smem);
 #ifdef CBIM_EMU
   const unsigned lds_base = 0;
 #else
@@ -217,8 +137,8 @@ __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
     const unsigned row = (unsigned)r0 + ((unsigned)lane >> 2);
     h_hh[q] = (row * 205u) >> 11;                     // row / 10 (row < 100)
     h_hw[q] = row - h_hh[q] * 10u;
-    const unsigned slot_src = (((unsigned)lane & 3u) ^ wr_swz(h_hh[q])) << 4;
-    h_off[q] = wr_mul24(wr_mul24(h_hh[q], (unsigned)p.Wi) + h_hw[q], x_sb) + slot_src;
+    const unsigned slot_src = (((unsigned)lane & 3u) ^ halo_swz(h_hh[q])) << 4;
+    h_off[q] = umul24(umul24(h_hh[q], (unsigned)p.Wi) + h_hw[q], x_sb) + slot_src;
     // (a last block of fewer than 32 channels — Cin = 48: the slots past the tensor's channels hold the next voxel's; zeros land in
     //  LDS instead and the gradient rows / columns they feed are not written)
     if ((unsigned)(ib * 64) + slot_src >= (unsigned)p.cin_bytes) h_off[q] = WR_OOB;
@@ -228,9 +148,9 @@ __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
   const int dj = WV == 8 ? (wv_u & 3) : wv_u, dp0 = WV == 8 ? (wv_u >> 2) : 0, dstep = WV == 8 ? 2 : 1;
   const unsigned d_row = 16u * (unsigned)dj + ((unsigned)lane >> 2);        // row (h, w) of the 8x8 plane
   const unsigned d_h = d_row >> 3, d_w = d_row & 7u;
-  const unsigned d_slot_src = (((unsigned)lane & 3u) ^ wr_swz(d_h)) << 4;
+  const unsigned d_slot_src = (((unsigned)lane & 3u) ^ halo_swz(d_h)) << 4;
   const unsigned d_off = (unsigned)(cb * 64) + d_slot_src < (unsigned)p.cout_bytes
-                             ? wr_mul24(wr_mul24(d_h, (unsigned)p.Wo) + d_w, dy_sb) + d_slot_src : WR_OOB;
+                             ? umul24(umul24(d_h, (unsigned)p.Wo) + d_w, dy_sb) + d_slot_src : WR_OOB;
 
   struct TilePos { int n, td, th, tw; };
   auto advance = [&](TilePos& u) {
@@ -269,15 +189,15 @@ __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
   auto dma_halo = [&](const Src& r, int q, int pl, unsigned buf) {
     const int d = r.id0 + pl;
     const bool in = (unsigned)d < (unsigned)p.Di;
-    wr_bdma16(r.hv[q], r.hbase, in ? 0x80000000u : 0u, in ? r.hsoff0 + (unsigned)d * r.hplane : 0u, smem, lds_base,
-              buf + (unsigned)pl * 6400u + h_lds[q]);
+    lds_dma16_buf(r.hv[q], r.hbase, in ? 0x80000000u : 0u, in ? r.hsoff0 + (unsigned)d * r.hplane : 0u, smem, lds_base,
+                  buf + (unsigned)pl * 6400u + h_lds[q]);
   };
   // this wave's k-th dy piece of the tile
   auto dma_dy = [&](const Src& r, int k) {
     const int pl = dp0 + dstep * k, d = r.od0 + pl;
     const bool in = d < p.Do;
-    wr_bdma16(r.dv, r.dbase, in ? 0x80000000u : 0u, in ? r.dsoff0 + (unsigned)d * r.dplane : 0u, smem, lds_base,
-              WR_DY + (unsigned)(pl * 64 + 16 * dj) * 64u);
+    lds_dma16_buf(r.dv, r.dbase, in ? 0x80000000u : 0u, in ? r.dsoff0 + (unsigned)d * r.dplane : 0u, smem, lds_base,
+                  WR_DY + (unsigned)(pl * 64 + 16 * dj) * 64u);
   };
 
   // ---- fragment addresses.  A transposed read: lane s of a 16-lane group supplies the address of voxel (s >> 2) [+4],
@@ -289,19 +209,19 @@ __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
   unsigned a_base[NCH];
 #pragma unroll
   for (int c = 0; c < NCH; ++c)
-    a_base[c] = WR_DY + (a_h * 8u + ((unsigned)lv >> 2)) * 64u + ((((unsigned)(2 * (ch0 + c)) + (((unsigned)lv & 3u) >> 1)) ^ wr_swz(a_h)) << 4) + sub;
+    a_base[c] = WR_DY + (a_h * 8u + ((unsigned)lv >> 2)) * 64u + ((((unsigned)(2 * (ch0 + c)) + (((unsigned)lv & 3u) >> 1)) ^ halo_swz(a_h)) << 4) + sub;
   unsigned b_base[3];
 #pragma unroll
   for (int kh = 0; kh < 3; ++kh) {
     const unsigned hh = a_h + (unsigned)kh;
-    b_base[kh] = (hh * 10u + ((unsigned)lv >> 2)) * 64u + ((((unsigned)(2 * cih) + (((unsigned)lv & 3u) >> 1)) ^ wr_swz(hh)) << 4) + sub;
+    b_base[kh] = (hh * 10u + ((unsigned)lv >> 2)) * 64u + ((((unsigned)(2 * cih) + (((unsigned)lv & 3u) >> 1)) ^ halo_swz(hh)) << 4) + sub;
   }
 
-  wr_f32x4 acc[NCH][27];
+  f32x4 acc[NCH][27];
 #pragma unroll
   for (int c = 0; c < NCH; ++c)
 #pragma unroll
-    for (int tp = 0; tp < 27; ++tp) acc[c][tp] = wr_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int tp = 0; tp < 27; ++tp) acc[c][tp] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int n_my = t_end - t_begin;
   if (n_my > 0) {
@@ -315,7 +235,7 @@ __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
 #pragma unroll
         for (int pl = 0; pl < 10; ++pl) dma_halo(r0s, q, pl, 0);
       }
-    wr_wait_vm0();
+    wait_vm<0>();
     __syncthreads();
   }
 #ifdef CBIM_WR32_PROF
@@ -331,12 +251,12 @@ __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
     for (int c = 0; c < NCH; ++c)
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const u32x2 a0 = wr_tr16_b64(smem + a_base[c] + (unsigned)i * 4096u);
-        const u32x2 a1 = wr_tr16_b64(smem + a_base[c] + (unsigned)i * 4096u + 256u);
+        const u32x2 a0 = lds_tr16_b64(smem + a_base[c] + (unsigned)i * 4096u);
+        const u32x2 a1 = lds_tr16_b64(smem + a_base[c] + (unsigned)i * 4096u + 256u);
         af[c][i] = u32x4{a0.x, a0.y, a1.x, a1.y};
       }
     if (more) {
-      wr_wait_lgkm0();                                                 // the reads have returned their data
+      wait_lgkm0();                                                 // the reads have returned their data
       WR_STAMP(1);                                                     // dy fragment reads
       __syncthreads();
       WR_STAMP(2);                                                     // barrier (dy region free)
@@ -351,8 +271,8 @@ __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
       auto frag = [&](int e) -> u32x4 {                                // e = (kh*3 + kw) * PLN + plane
         const int pl = e % PLN, s = e / PLN;
         const unsigned a = buf + b_base[s / 3] + (unsigned)((s % 3) * 64) + (unsigned)(pl * 6400);
-        const u32x2 b0 = wr_tr16_b64(smem + a);
-        const u32x2 b1 = wr_tr16_b64(smem + a + 256u);
+        const u32x2 b0 = lds_tr16_b64(smem + a);
+        const u32x2 b1 = lds_tr16_b64(smem + a + 256u);
         return u32x4{b0.x, b0.y, b1.x, b1.y};
       };
 #pragma unroll
@@ -378,7 +298,7 @@ __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
         for (int pl = 0; pl < PLN; ++pl) {
           const int e = s * PLN + pl;
           if (e + RING - 1 < SEQ && !(WR_DBG & 4)) xr[(e + RING - 1) % RING] = frag(e + RING - 1);
-          WR_SCHED_FENCE();
+          CBIM_SCHED_FENCE();
 #if WR32_SETPRIO && !defined(CBIM_EMU)
           __builtin_amdgcn_s_setprio(3);
 #endif
@@ -399,14 +319,14 @@ __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
 #if WR32_SETPRIO && !defined(CBIM_EMU)
           __builtin_amdgcn_s_setprio(0);
 #endif
-          WR_SCHED_FENCE();
+          CBIM_SCHED_FENCE();
         }
       }
     }
     // (C) ONE barrier per tile (two with the dy hand-over): every wave is done with `buf`, the other buffer and the dy
     //     tile are complete (own LDS-DMA pieces waited for)
     WR_STAMP(4);                                                       // MFMA loop (+ halo pieces)
-    wr_wait_vm0();
+    wait_vm<0>();
     WR_STAMP(5);                                                       // own pieces landed
     __syncthreads();
     WR_STAMP(6);                                                       // barrier

@@ -9,12 +9,7 @@
 //                         forms from 0/1 masks are these integers, so the host reproduces its arithmetic bit for bit
 // All HBM-bound streaming kernels on NCDHW float32 probabilities (the layout the model head emits).
 #include "cbim_common.h"
-
-#ifdef CBIM_EMU
-#define CBIM_DYN_SMEM(name) unsigned char* name = cbim_emu::dyn_smem()
-#else
-#define CBIM_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
-#endif
+#include "gfx950_prims.h"
 
 namespace cbim {
 

@@ -33,29 +33,18 @@
 // (profiles/r06_h .. r06_n_medformer_kernels.txt; the aten::mm launches it replaces take ~11 us each.)  fp32 FMA chains in a fixed
 // order: bit-reproducible.
 #include "cbim_common.h"
+#include "gfx950_prims.h"
 
 namespace cbim {
 
 static constexpr int MG_T = 256, MG_OT = 16, MG_KC = 64, MG_PA = 20;
 
-// butterfly partner inside a quad / a row of 16 lanes by DPP (no LDS round trip; __shfl_xor is a ds_bpermute: ~100 cycles each —
-// twelve dependent ones per map row made the normalisation 10 us per chunk), across rows by ds_bpermute
-template <int MSK>
-__device__ __forceinline__ float mg_bfly(float v) {
-#ifdef CBIM_EMU
-  return __shfl_xor(v, MSK, 64);
-#else
-  if (MSK >= 16) return __shfl_xor(v, MSK, 64);
-  constexpr int ctrl = MSK == 1 ? 0xB1 : MSK == 2 ? 0x4E : MSK == 4 ? 0x141 : 0x140;   // quad_perm [1,0,3,2] / [2,3,0,1], row_half_mirror, row_mirror
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, false));
-#endif
-}
 __device__ __forceinline__ float mg_wave_sum(float v) {
-  v += mg_bfly<1>(v); v += mg_bfly<2>(v); v += mg_bfly<4>(v); v += mg_bfly<8>(v); v += mg_bfly<16>(v); v += mg_bfly<32>(v);
+  v += dpp_bfly<1>(v); v += dpp_bfly<2>(v); v += dpp_bfly<4>(v); v += dpp_bfly<8>(v); v += dpp_bfly<16>(v); v += dpp_bfly<32>(v);
   return v;
 }
 __device__ __forceinline__ float mg_quad_sum(float v) {
-  v += mg_bfly<1>(v); v += mg_bfly<2>(v);
+  v += dpp_bfly<1>(v); v += dpp_bfly<2>(v);
   return v;
 }
 

@@ -16,14 +16,9 @@
 // Layout: feature maps channels-last [N][L][C]; head split is the reference's "(dim_head heads)":
 // channel c = d*heads + h (medformer_utils.py:43-51).  Map-side tensors are float32 [N][M][inner].
 #include "cbim_common.h"
+#include "gfx950_prims.h"
 #include "conv_wgrad_r32.h"
 #include <stdlib.h>
-
-#ifdef CBIM_EMU
-#define CBIM_DYN_SMEM(name) unsigned char* name = cbim_emu::dyn_smem()
-#else
-#define CBIM_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
-#endif
 
 namespace cbim {
 
@@ -158,21 +153,20 @@ static constexpr int WT = 4;
 // activation.  Packed f32 pairs throughout (v_pk_add / v_pk_mul / v_pk_fma_f32): the kernel is vector-ALU bound (27 taps x 8
 // channels per output against 32 bytes of traffic), and as scalar fmaf + a run-time activation switch per element it spent
 // ~750 lane-instructions per output chunk (52 us per call on the 4x-expanded MBConv tensors of MedFormer).
-typedef float dw_f2 __attribute__((ext_vector_type(2)));
 template <typename T> struct DwPairs;
 template <> struct DwPairs<bf16_tag> {
   static constexpr int NP = 4;
-  static __device__ __forceinline__ void unpack(const u32x4& v, dw_f2* f) {
+  static __device__ __forceinline__ void unpack(const u32x4& v, f32x2* f) {
     const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) f[j] = dw_f2{__uint_as_float(w[j] << 16), __uint_as_float(w[j] & 0xffff0000u)};
+    for (int j = 0; j < 4; ++j) f[j] = f32x2{__uint_as_float(w[j] << 16), __uint_as_float(w[j] & 0xffff0000u)};
   }
 };
 template <> struct DwPairs<float> {
   static constexpr int NP = 2;
-  static __device__ __forceinline__ void unpack(const u32x4& v, dw_f2* f) {
-    f[0] = dw_f2{__uint_as_float(v.x), __uint_as_float(v.y)};
-    f[1] = dw_f2{__uint_as_float(v.z), __uint_as_float(v.w)};
+  static __device__ __forceinline__ void unpack(const u32x4& v, f32x2* f) {
+    f[0] = f32x2{__uint_as_float(v.x), __uint_as_float(v.y)};
+    f[1] = f32x2{__uint_as_float(v.z), __uint_as_float(v.w)};
   }
 };
 
@@ -221,18 +215,18 @@ __global__ void __launch_bounds__(NT) k_dwconv3(const void* __restrict__ x, int6
     const int ho = (int)(r % (unsigned)H); r /= (unsigned)H;
     const int dz = (int)(r % (unsigned)D);
     const int64_t n = r / (unsigned)D;
-    dw_f2 nmean[NP], rstd[NP], bs[NP], acc[WT][NP];
+    f32x2 nmean[NP], rstd[NP], bs[NP], acc[WT][NP];
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-      nmean[j] = dw_f2{0.f, 0.f}; rstd[j] = dw_f2{1.f, 1.f}; bs[j] = dw_f2{0.f, 0.f};
+      nmean[j] = f32x2{0.f, 0.f}; rstd[j] = f32x2{1.f, 1.f}; bs[j] = f32x2{0.f, 0.f};
       if (MODE != 0) {
         const float* st = in_stats + ((size_t)n * C + c0 + 2 * j) * 2;
-        nmean[j] = dw_f2{-st[0], -st[2]};
-        rstd[j] = dw_f2{st[1], st[3]};
+        nmean[j] = f32x2{-st[0], -st[2]};
+        rstd[j] = f32x2{st[1], st[3]};
       }
-      if (bias) bs[j] = dw_f2{bias[(size_t)n * C + c0 + 2 * j], bias[(size_t)n * C + c0 + 2 * j + 1]};
+      if (bias) bs[j] = f32x2{bias[(size_t)n * C + c0 + 2 * j], bias[(size_t)n * C + c0 + 2 * j + 1]};
 #pragma unroll
-      for (int o = 0; o < WT; ++o) acc[o][j] = dw_f2{0.f, 0.f};
+      for (int o = 0; o < WT; ++o) acc[o][j] = f32x2{0.f, 0.f};
     }
     for (int a = 0; a < kD; ++a) {
       const int dd = dz + a - pD;
@@ -244,7 +238,7 @@ __global__ void __launch_bounds__(NT) k_dwconv3(const void* __restrict__ x, int6
         // one 64-bit row pointer per (kd,kh); the WT+2 chunks are xs elements apart
         const unsigned char* rp = (const unsigned char*)x + ((int64_t)(rbase + w0 - 1) * xs + c0) * (int64_t)Elem<T>::SIZE;
         const unsigned xsb = (unsigned)xs * Elem<T>::SIZE;
-        dw_f2 in[WT + 2][NP];
+        f32x2 in[WT + 2][NP];
 #pragma unroll
         for (int q = 0; q < WT + 2; ++q) {
           const int ww = w0 - 1 + q;
@@ -252,25 +246,25 @@ __global__ void __launch_bounds__(NT) k_dwconv3(const void* __restrict__ x, int6
             DwPairs<T>::unpack(*(const u32x4*)(rp + (size_t)q * xsb), in[q]);
 #pragma unroll
             for (int j = 0; j < NP; ++j) {
-              dw_f2 v = in[q][j];
+              f32x2 v = in[q][j];
               if (MODE != 0) {
                 v = (v + nmean[j]) * rstd[j];
-                if (MODE == 1) v = __builtin_elementwise_max(v, dw_f2{0.f, 0.f});
-                if (MODE == 3) v = dw_f2{act_fwd(v.x, act), act_fwd(v.y, act)};
+                if (MODE == 1) v = __builtin_elementwise_max(v, f32x2{0.f, 0.f});
+                if (MODE == 3) v = f32x2{act_fwd(v.x, act), act_fwd(v.y, act)};
               }
               in[q][j] = v + bs[j];
             }
           } else {
 #pragma unroll
-            for (int j = 0; j < NP; ++j) in[q][j] = dw_f2{0.f, 0.f};
+            for (int j = 0; j < NP; ++j) in[q][j] = f32x2{0.f, 0.f};
           }
         }
         const float* wt = w_s + ((a * kH + b) * 3) * (DG * CPC) + cl * CPC;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          dw_f2 wv[NP];
+          f32x2 wv[NP];
 #pragma unroll
-          for (int j = 0; j < NP; ++j) wv[j] = dw_f2{wt[c * (DG * CPC) + 2 * j], wt[c * (DG * CPC) + 2 * j + 1]};
+          for (int j = 0; j < NP; ++j) wv[j] = f32x2{wt[c * (DG * CPC) + 2 * j], wt[c * (DG * CPC) + 2 * j + 1]};
 #pragma unroll
           for (int o = 0; o < WT; ++o)
 #pragma unroll
@@ -339,16 +333,16 @@ __global__ void __launch_bounds__(NT) k_dwconv3_lds(const void* __restrict__ x, 
   constexpr int VPT = NT / LG;                        // halo voxels per sweep of the workgroup
   const bool c_ok = cl < G;
   const int c0 = (g0 + (c_ok ? cl : 0)) * CPC;
-  dw_f2 nmean[NP], rstd[NP], bs[NP];
+  f32x2 nmean[NP], rstd[NP], bs[NP];
 #pragma unroll
   for (int j = 0; j < NP; ++j) {
-    nmean[j] = dw_f2{0.f, 0.f}; rstd[j] = dw_f2{1.f, 1.f}; bs[j] = dw_f2{0.f, 0.f};
+    nmean[j] = f32x2{0.f, 0.f}; rstd[j] = f32x2{1.f, 1.f}; bs[j] = f32x2{0.f, 0.f};
     if (MODE != 0) {
       const float* st = in_stats + ((size_t)n * C + c0 + 2 * j) * 2;
-      nmean[j] = dw_f2{-st[0], -st[2]};
-      rstd[j] = dw_f2{st[1], st[3]};
+      nmean[j] = f32x2{-st[0], -st[2]};
+      rstd[j] = f32x2{st[1], st[3]};
     }
-    if (bias) bs[j] = dw_f2{bias[(size_t)n * C + c0 + 2 * j], bias[(size_t)n * C + c0 + 2 * j + 1]};
+    if (bias) bs[j] = f32x2{bias[(size_t)n * C + c0 + 2 * j], bias[(size_t)n * C + c0 + 2 * j + 1]};
   }
   const int hV = hD * hH * hW;
   constexpr int UL = 10;                              // loads in flight per thread and trip: the 600-voxel halo in one sweep
@@ -370,16 +364,16 @@ __global__ void __launch_bounds__(NT) k_dwconv3_lds(const void* __restrict__ x, 
       if (hv < hV) {
         u32x4 o = u32x4{0u, 0u, 0u, 0u};
         if (in[u]) {
-          dw_f2 f[NP];
+          f32x2 f[NP];
           DwPairs<T>::unpack(raw[u], f);
           float g[CPC];
 #pragma unroll
           for (int j = 0; j < NP; ++j) {
-            dw_f2 v = f[j];
+            f32x2 v = f[j];
             if (MODE != 0) {
               v = (v + nmean[j]) * rstd[j];
-              if (MODE == 1) v = __builtin_elementwise_max(v, dw_f2{0.f, 0.f});
-              if (MODE == 3) v = dw_f2{act_fwd(v.x, act), act_fwd(v.y, act)};
+              if (MODE == 1) v = __builtin_elementwise_max(v, f32x2{0.f, 0.f});
+              if (MODE == 3) v = f32x2{act_fwd(v.x, act), act_fwd(v.y, act)};
             }
             v = v + bs[j];
             g[2 * j] = v.x; g[2 * j + 1] = v.y;
@@ -398,23 +392,23 @@ __global__ void __launch_bounds__(NT) k_dwconv3_lds(const void* __restrict__ x, 
     const int sw = sidx % (LTW / WT), r = sidx / (LTW / WT), sh = r % LTH, sd = r / LTH;
     const int dz = d0 + sd, ho = h0 + sh, wo = w0t + sw * WT;
     if (dz >= D || ho >= H || wo >= W) continue;
-    dw_f2 acc[WT][NP];
+    f32x2 acc[WT][NP];
 #pragma unroll
     for (int o = 0; o < WT; ++o)
 #pragma unroll
-      for (int j = 0; j < NP; ++j) acc[o][j] = dw_f2{0.f, 0.f};
+      for (int j = 0; j < NP; ++j) acc[o][j] = f32x2{0.f, 0.f};
     for (int a = 0; a < kD; ++a)
       for (int b = 0; b < kH; ++b) {
         const unsigned char* rp = halo_s + ((size_t)(((sd + a) * hH + sh + b) * hW + sw * WT) * LG + cl) * 16;
-        dw_f2 inr[WT + 2][NP];
+        f32x2 inr[WT + 2][NP];
 #pragma unroll
         for (int q = 0; q < WT + 2; ++q) DwPairs<T>::unpack(*(const u32x4*)(rp + (size_t)q * LG * 16), inr[q]);
         const float* wt = w_s + ((a * kH + b) * 3) * (LG * CPC) + cl * CPC;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          dw_f2 wv[NP];
+          f32x2 wv[NP];
 #pragma unroll
-          for (int j = 0; j < NP; ++j) wv[j] = dw_f2{wt[c * (LG * CPC) + 2 * j], wt[c * (LG * CPC) + 2 * j + 1]};
+          for (int j = 0; j < NP; ++j) wv[j] = f32x2{wt[c * (LG * CPC) + 2 * j], wt[c * (LG * CPC) + 2 * j + 1]};
 #pragma unroll
           for (int o = 0; o < WT; ++o)
 #pragma unroll
@@ -653,21 +647,21 @@ __global__ void __launch_bounds__(NT) k_dwconv3_wgrad_lds(const void* __restrict
   const bool active = cl < G;
   // packed f32 pairs (v_pk_fma_f32): 12 instead of 24 multiply-add instructions per LDS read pair
   constexpr int NP2 = CPC / 2;
-  dw_f2 acc2[3][NP2];
+  f32x2 acc2[3][NP2];
 #pragma unroll
   for (int c = 0; c < 3; ++c)
 #pragma unroll
-    for (int j = 0; j < NP2; ++j) acc2[c][j] = dw_f2{0.f, 0.f};
+    for (int j = 0; j < NP2; ++j) acc2[c][j] = f32x2{0.f, 0.f};
   if (active) {
     for (int r = rs; r < TH; r += 3) {
-      const dw_f2* xr = (const dw_f2*)(x_s + ((size_t)((ka * hH + r + kb) * hW) * WG_CH + cl) * CPC);
-      const dw_f2* gr = (const dw_f2*)(g_s + ((size_t)(r * W) * WG_CH + cl) * CPC);
+      const f32x2* xr = (const f32x2*)(x_s + ((size_t)((ka * hH + r + kb) * hW) * WG_CH + cl) * CPC);
+      const f32x2* gr = (const f32x2*)(g_s + ((size_t)(r * W) * WG_CH + cl) * CPC);
       const int RS = WG_CH * CPC / 2;                     // pairs per LDS voxel row
-      dw_f2 x0[NP2], x1[NP2];
+      f32x2 x0[NP2], x1[NP2];
 #pragma unroll
       for (int j = 0; j < NP2; ++j) { x0[j] = xr[j]; x1[j] = xr[RS + j]; }
       for (int w = 0; w < W; ++w) {
-        dw_f2 x2[NP2], g[NP2];
+        f32x2 x2[NP2], g[NP2];
 #pragma unroll
         for (int j = 0; j < NP2; ++j) {
           x2[j] = xr[(size_t)(w + 2) * RS + j];

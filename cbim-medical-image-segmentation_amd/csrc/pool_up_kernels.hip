@@ -8,6 +8,7 @@
 // unet_utils.py:69-71.  Index/weight arithmetic follows ATen's align_corners rule:
 // scale=(in-1)/(out-1) (0 if out==1), src=scale*dst, i0=(int)src, i1=min(i0+1,in-1), l1=src-i0.
 #include "cbim_common.h"
+#include "gfx950_prims.h"
 #include "up_lerp.h"
 
 namespace cbim {
@@ -88,23 +89,6 @@ __global__ void __launch_bounds__(NT) k_maxpool_bwd(const void* __restrict__ dy,
     st_chunk<T>(dx, row * C + (size_t)cc * CPC, Elem<T>::pack(f));
   }
   }
-}
-
-// ---- trilinear align_corners source index ------------------------------------------------------
-struct Lin { int i0, i1; float l0, l1; };
-__device__ __forceinline__ float lin_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
-__device__ __forceinline__ Lin lin_src(int dst, float scale, int in) {
-  float src = scale * (float)dst;
-  int i0 = (int)src;
-  if (i0 > in - 1) i0 = in - 1;
-  float l1 = src - (float)i0;
-  l1 = l1 < 0.f ? 0.f : (l1 > 1.f ? 1.f : l1);
-  Lin r;
-  r.i0 = i0;
-  r.i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  r.l1 = l1;
-  r.l0 = 1.f - l1;
-  return r;
 }
 
 template <typename T>

@@ -6,6 +6,7 @@
 //   head: outc = nn.Conv3d(base, classes, 1) with bias (unet.py:47): channels-last T in, NCDHW fp32
 //         logits out (the layout nn.CrossEntropyLoss / DiceLoss consume, train.py:212).
 #include "cbim_common.h"
+#include "gfx950_prims.h"
 #include <stdlib.h>
 
 namespace cbim {
@@ -20,12 +21,6 @@ struct StemParams {
   int tiles_d, tiles_h, tiles_w, hD, hH, hW, taps;
   int strips_per_n, tiles_per_strip;
 };
-
-#ifdef CBIM_EMU
-#define CBIM_DYN_SMEM(name) unsigned char* name = cbim_emu::dyn_smem()
-#else
-#define CBIM_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
-#endif
 
 // tile = 4 x 8 x 8 output voxels, one thread per voxel, 8 couts per register pass.
 template <typename T>
@@ -177,33 +172,6 @@ __global__ void __launch_bounds__(NT) k_stem_fwd_mfma(StemParams p) {
   }
 }
 
-// LDS transpose read / wave-level LDS fence of the matrix-core kernels below
-__device__ __forceinline__ u32x2 hd_tr16_b64(const unsigned char* p) {
-#ifdef CBIM_EMU
-  unsigned short o[4];
-  emu_ds_read_tr16_b64(p, o);
-  u32x2 r;
-  r.x = (unsigned)o[0] | ((unsigned)o[1] << 16);
-  r.y = (unsigned)o[2] | ((unsigned)o[3] << 16);
-  return r;
-#else
-  typedef __attribute__((ext_vector_type(4))) short s16x4;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
-  return __builtin_bit_cast(u32x2, v);
-#endif
-}
-// LDS written by some lanes of the wave, read by others: DS instructions of a wave execute in order, so only the compiler
-// (and the host-side executor, whose lanes are fibers) needs a fence
-__device__ __forceinline__ void hd_wave_sync() {
-#ifdef CBIM_EMU
-  (void)__any(0);
-#else
-  asm volatile("" ::: "memory");
-#endif
-}
-
-
 // ---- stem weight gradient on the matrix cores: one input channel, bf16 dy rows of Cout = 32 * CP channels ------------------
 // dw[co][tap] = sum_v dy[v][co] x[v + tap]: v_mfma_f32_16x16x32_bf16 contracting over 32 VOXELS (4 w-rows of the 4x8x8 tile).
 // A = dy^T through the LDS transpose read (as k_wgrad_r32), B = the im2col column of a tap: the 8 voxels of a w-row are 8
@@ -295,7 +263,7 @@ __global__ void __launch_bounds__(NT) k_stem_wgrad_mfma(StemParams p) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           const unsigned char* a = dyL + (size_t)(td * 64 + th0 * 8 + 8 * g + (li >> 2)) * ROWB + (32 * q + 16 * u) * 2 + (li & 3) * 8;
-          const u32x2 a0 = hd_tr16_b64(a), a1 = hd_tr16_b64(a + 4 * ROWB);
+          const u32x2 a0 = lds_tr16_b64(a), a1 = lds_tr16_b64(a + 4 * ROWB);
           const u32x4 af = u32x4{a0.x, a0.y, a1.x, a1.y};
 #pragma unroll
           for (int tt = 0; tt < 2; ++tt) {
@@ -932,16 +900,16 @@ __global__ void __launch_bounds__(HM_NW * 64) k_head_bwd_mfma(const void* __rest
       for (int j = 0; j < 8; ++j) lo[j] = d[j] - h[j];
     }
     const u32x4 alo = Elem<bf16_tag>::pack(lo);
-    hd_wave_sync();                                                      // the previous step's LDS reads are done
+    wave_sync();                                                      // the previous step's LDS reads are done
 #pragma unroll
     for (int u = 0; u < NX; ++u) *(u32x4*)(xs + (size_t)(lane + 64 * u) * 16) = xr[slot][u];
     *(u32x4*)(dzs + li * 64 + g * 16) = ahi;
-    hd_wave_sync();
+    wave_sync();
     // dw: contraction over the 32 voxels
 #pragma unroll
     for (int ct = 0; ct < HC; ++ct) {
       const unsigned char* a = xs + (8 * g + (li >> 2)) * ROWB + ct * 32 + (li & 3) * 8;
-      const u32x2 b0 = hd_tr16_b64(a), b1 = hd_tr16_b64(a + 4 * ROWB);
+      const u32x2 b0 = lds_tr16_b64(a), b1 = lds_tr16_b64(a + 4 * ROWB);
       const u32x4 bf = u32x4{b0.x, b0.y, b1.x, b1.y};
       acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ahi), __builtin_bit_cast(bf16x8, bf), acc[ct], 0, 0, 0);
       acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, alo), __builtin_bit_cast(bf16x8, bf), acc[ct], 0, 0, 0);
@@ -951,7 +919,7 @@ __global__ void __launch_bounds__(HM_NW * 64) k_head_bwd_mfma(const void* __rest
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const unsigned char* a = dzs + ((8 * g + (li >> 2)) & 15) * 64 + h * 32 + (li & 3) * 8;
-        u32x2 e0 = hd_tr16_b64(a), e1 = hd_tr16_b64(a + 4 * 64);
+        u32x2 e0 = lds_tr16_b64(a), e1 = lds_tr16_b64(a + 4 * 64);
         if (g >= 2) { e0 = u32x2{0u, 0u}; e1 = u32x2{0u, 0u}; }
         const u32x4 ef = u32x4{e0.x, e0.y, e1.x, e1.y};
 #pragma unroll

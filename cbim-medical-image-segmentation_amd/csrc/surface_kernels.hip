@@ -13,14 +13,9 @@
 //                       own code) to that mask's list (one global atomic per workgroup and 32-row chunk)
 // The minimum over a line is taken by comparison only, so it is exact whatever the spacing; ties pick offsets of equal length.
 #include "cbim_common.h"
+#include "gfx950_prims.h"
 
 #include <limits.h>
-
-#ifdef CBIM_EMU
-#define CBIM_DYN_SMEM(name) unsigned char* name = cbim_emu::dyn_smem()
-#else
-#define CBIM_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
-#endif
 
 namespace cbim {
 

@@ -23,15 +23,10 @@
 // (even / odd keys own separate histograms) —
 // and the per-workgroup histograms are summed over windows in launch order.
 #include "swin_common.h"
+#include "gfx950_prims.h"
 #include <stdlib.h>
 
 namespace cbim {
-
-#ifdef CBIM_EMU
-#define CBIM_DYN_SMEM(name) unsigned char* name = cbim_emu::dyn_smem()
-#else
-#define CBIM_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
-#endif
 
 struct WinSmem {
   float* A;       // [n][DH]  K   (pass B: scaled Q)

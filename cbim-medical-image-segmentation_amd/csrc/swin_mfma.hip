@@ -25,6 +25,7 @@
 // (the last window along a shifted dimension), the key-exists test only in a window's last block, and the softmax
 // denominator as row 16 of the P.V product (a row of ones appended to V^T).
 #include "swin_common.h"
+#include "gfx950_prims.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -41,7 +42,6 @@ static constexpr unsigned WM_W = WM_PAD * 4;             // one [352] word array
 // Table gathers and histogram atomics take ABSOLUTE 32-bit LDS addresses (the workgroup's LDS base folded into the
 // per-token words at staging): one v_sub per access, no generic-pointer arithmetic in the inner loops.
 #ifdef CBIM_EMU
-#define WM_DYN_SMEM(name) unsigned char* name = cbim_emu::dyn_smem()
 __device__ __forceinline__ float wm_exp2(float x) { return exp2f(x); }
 __device__ __forceinline__ float wm_log2(float x) { return log2f(x); }
 __device__ __forceinline__ unsigned wm_lds_addr(const unsigned char* smem, unsigned off) { (void)smem; return off; }
@@ -51,7 +51,6 @@ __device__ __forceinline__ void wm_lds_add64(unsigned char* smem, unsigned a, un
 }
 __device__ __forceinline__ float wm_fract(float x) { return x - floorf(x); }
 #else
-#define WM_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
 __device__ __forceinline__ float wm_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float wm_log2(float x) { return __builtin_amdgcn_logf(x); }
 typedef __attribute__((address_space(3))) float wm_lds_float;
@@ -201,7 +200,7 @@ __global__ void __launch_bounds__(WM_NT, 2) k_winattn_fwd_mfma(WinGeom g, const 
                                                                const float* __restrict__ qkv_bias,
                                                                const float* __restrict__ table, void* __restrict__ out,
                                                                float* __restrict__ lse_out) {
-  WM_DYN_SMEM(smem);
+  CBIM_DYN_SMEM(smem);
   const int n = g.w0 * g.w1 * g.w2, TS = (2 * g.tw0 - 1) * (2 * g.tw1 - 1) * (2 * g.tw2 - 1);
   const int off0 = ((g.tw0 - 1) * (2 * g.tw1 - 1) + (g.tw1 - 1)) * (2 * g.tw2 - 1) + (g.tw2 - 1);
   const int win = blockIdx.x, hd = blockIdx.y, tid = threadIdx.x;
@@ -473,7 +472,7 @@ __global__ void __launch_bounds__(WB_NT) k_winattn_bwd_mfma(WinGeom g, const voi
                                                             const float* __restrict__ lse_in, void* __restrict__ dqkv,
                                                             float* __restrict__ part_tbl, float* __restrict__ part_pad,
                                                             int dbg) {
-  WM_DYN_SMEM(smem);
+  CBIM_DYN_SMEM(smem);
   const int n = g.w0 * g.w1 * g.w2, TS = (2 * g.tw0 - 1) * (2 * g.tw1 - 1) * (2 * g.tw2 - 1);
   const int off0 = ((g.tw0 - 1) * (2 * g.tw1 - 1) + (g.tw1 - 1)) * (2 * g.tw2 - 1) + (g.tw2 - 1);
   const int win = blockIdx.x, hd = blockIdx.y, tid = threadIdx.x;

@@ -1,4 +1,4 @@
-// up_lerp.h — the one trilinear interpolation arithmetic every up-sampling kernel shares (pool_up_kernels.hip,
+// up_lerp.h — the one trilinear index and interpolation arithmetic every up-sampling kernel shares (pool_up_kernels.hip,
 // up_tile_kernels.hip): results are bit-identical whichever kernel forms them (tests compare the paths with torch.equal).
 //
 // Eight corner chunks (16 bytes each: CPC channels of one coarse voxel), order [(a * 2 + b) * 2 + c] with a / b / c = lower or
@@ -11,22 +11,38 @@
 
 namespace cbim {
 
-typedef float up_f2 __attribute__((ext_vector_type(2)));
+// trilinear align_corners source index, ATen's rule: scale = (in - 1) / (out - 1) (0 if out == 1), src = scale * dst,
+// i0 = (int)src, i1 = min(i0 + 1, in - 1), l1 = src - i0 (float scale, truncation)
+struct Lin { int i0, i1; float l0, l1; };
+__device__ __forceinline__ float lin_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
+__device__ __forceinline__ Lin lin_src(int dst, float scale, int in) {
+  float src = scale * (float)dst;
+  int i0 = (int)src;
+  if (i0 > in - 1) i0 = in - 1;
+  float l1 = src - (float)i0;
+  l1 = l1 < 0.f ? 0.f : (l1 > 1.f ? 1.f : l1);
+  Lin r;
+  r.i0 = i0;
+  r.i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  r.l1 = l1;
+  r.l0 = 1.f - l1;
+  return r;
+}
 
 template <typename T> struct UpPairs;
 template <> struct UpPairs<bf16_tag> {
   static constexpr int NP = 4;    // f32 pairs per 16-byte chunk
-  static __device__ __forceinline__ void unpack(const u32x4& v, up_f2* f) {
+  static __device__ __forceinline__ void unpack(const u32x4& v, f32x2* f) {
     const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) f[j] = up_f2{__uint_as_float(w[j] << 16), __uint_as_float(w[j] & 0xffff0000u)};
+    for (int j = 0; j < 4; ++j) f[j] = f32x2{__uint_as_float(w[j] << 16), __uint_as_float(w[j] & 0xffff0000u)};
   }
 };
 template <> struct UpPairs<float> {
   static constexpr int NP = 2;
-  static __device__ __forceinline__ void unpack(const u32x4& v, up_f2* f) {
-    f[0] = up_f2{__uint_as_float(v.x), __uint_as_float(v.y)};
-    f[1] = up_f2{__uint_as_float(v.z), __uint_as_float(v.w)};
+  static __device__ __forceinline__ void unpack(const u32x4& v, f32x2* f) {
+    f[0] = f32x2{__uint_as_float(v.x), __uint_as_float(v.y)};
+    f[1] = f32x2{__uint_as_float(v.z), __uint_as_float(v.w)};
   }
 };
 
@@ -34,14 +50,14 @@ template <> struct UpPairs<float> {
 template <typename T>
 __device__ __forceinline__ void trilerp(const u32x4* c, float d0, float d1, float h0, float h1, float w0, float w1, float* out) {
   constexpr int NP = UpPairs<T>::NP;
-  const up_f2 W0 = {w0, w0}, W1 = {w1, w1}, H0 = {h0, h0}, H1 = {h1, h1}, D0 = {d0, d0}, D1 = {d1, d1};
-  up_f2 u[2][NP];
+  const f32x2 W0 = {w0, w0}, W1 = {w1, w1}, H0 = {h0, h0}, H1 = {h1, h1}, D0 = {d0, d0}, D1 = {d1, d1};
+  f32x2 u[2][NP];
 #pragma unroll
   for (int a = 0; a < 2; ++a) {
-    up_f2 t[2][NP];
+    f32x2 t[2][NP];
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-      up_f2 f0[NP], f1[NP];
+      f32x2 f0[NP], f1[NP];
       UpPairs<T>::unpack(c[(a * 2 + b) * 2], f0);
       UpPairs<T>::unpack(c[(a * 2 + b) * 2 + 1], f1);
 #pragma unroll
@@ -52,7 +68,7 @@ __device__ __forceinline__ void trilerp(const u32x4* c, float d0, float d1, floa
   }
 #pragma unroll
   for (int j = 0; j < NP; ++j) {
-    const up_f2 r = __builtin_elementwise_fma(D1, u[1][j], D0 * u[0][j]);
+    const f32x2 r = __builtin_elementwise_fma(D1, u[1][j], D0 * u[0][j]);
     out[2 * j] = r.x;
     out[2 * j + 1] = r.y;
   }

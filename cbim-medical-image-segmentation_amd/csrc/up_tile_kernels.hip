@@ -20,6 +20,7 @@
 // Shapes whose boxes do not fit the LDS budget stay on the gather kernels (the launchers return CBIM_EUNSUPPORTED and the
 // host side falls back — both paths are tested against each other bit for bit).
 #include "cbim_common.h"
+#include "gfx950_prims.h"
 #include "up_lerp.h"
 
 namespace cbim {
@@ -27,37 +28,6 @@ namespace cbim {
 static constexpr int UT = 256;                        // threads
 static constexpr int FD = 4, FH = 8, FW = 8;          // fine tile
 static constexpr int FV = FD * FH * FW;
-
-#ifdef CBIM_EMU
-#define UT_DYN_SMEM(name) unsigned char* name = cbim_emu::dyn_smem()
-#else
-#define UT_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
-#endif
-
-__device__ __forceinline__ unsigned ut_mad24(unsigned a, unsigned b, unsigned c) {
-#ifdef CBIM_EMU
-  return a * b + c;
-#else
-  return __umul24(a, b) + c;
-#endif
-}
-
-// trilinear align_corners source index (the arithmetic of pool_up_kernels.hip / ATen: float scale, truncation)
-struct ULin { int i0, i1; float l0, l1; };
-__device__ __forceinline__ float ulin_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
-__device__ __forceinline__ ULin ulin_src(int dst, float scale, int in) {
-  float src = scale * (float)dst;
-  int i0 = (int)src;
-  if (i0 > in - 1) i0 = in - 1;
-  float l1 = src - (float)i0;
-  l1 = l1 < 0.f ? 0.f : (l1 > 1.f ? 1.f : l1);
-  ULin r;
-  r.i0 = i0;
-  r.i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  r.l1 = l1;
-  r.l0 = 1.f - l1;
-  return r;
-}
 
 struct UpTileParams {
   const void* low; const void* skip; const void* g;
@@ -82,8 +52,8 @@ __device__ __forceinline__ void stage_box(const UpTileParams& p, unsigned char* 
   const int d0 = td * FD, h0 = th * FH, w0 = tw * FW;
   const int dl = d0 + FD - 1 < p.D ? d0 + FD - 1 : p.D - 1, hl = h0 + FH - 1 < p.H ? h0 + FH - 1 : p.H - 1,
             wl = w0 + FW - 1 < p.W ? w0 + FW - 1 : p.W - 1;
-  const int od = ulin_src(d0, sd, p.Dl).i0, oh = ulin_src(h0, sh, p.Hl).i0, ow = ulin_src(w0, sw, p.Wl).i0;   // box origin
-  const int ed = ulin_src(dl, sd, p.Dl).i1 - od + 1, eh = ulin_src(hl, sh, p.Hl).i1 - oh + 1, ew = ulin_src(wl, sw, p.Wl).i1 - ow + 1;
+  const int od = lin_src(d0, sd, p.Dl).i0, oh = lin_src(h0, sh, p.Hl).i0, ow = lin_src(w0, sw, p.Wl).i0;   // box origin
+  const int ed = lin_src(dl, sd, p.Dl).i1 - od + 1, eh = lin_src(hl, sh, p.Hl).i1 - oh + 1, ew = lin_src(wl, sw, p.Wl).i1 - ow + 1;
   const int cch = p.Cl / CPC;
   const unsigned rowb = (unsigned)p.Cl * ES;
   const int items = ed * eh * ew * cch;
@@ -100,7 +70,7 @@ __device__ __forceinline__ void stage_box(const UpTileParams& p, unsigned char* 
     if (tid < FD) { dst = d0 + tid; if (dst > p.D - 1) dst = p.D - 1; in = p.Dl; org = od; sc = sd; }
     else if (tid < FD + FH) { dst = h0 + tid - FD; if (dst > p.H - 1) dst = p.H - 1; in = p.Hl; org = oh; sc = sh; }
     else { dst = w0 + tid - FD - FH; if (dst > p.W - 1) dst = p.W - 1; in = p.Wl; org = ow; sc = sw; }
-    const ULin l = ulin_src(dst, sc, in);
+    const Lin l = lin_src(dst, sc, in);
     // byte offset of a box coordinate along this axis: the per-voxel address is then three adds (the products of run-time
     // extents were 16 quarter-rate 32-bit multiplies per output chunk)
     const int unit = (int)rowb * (tid < FD ? p.bh * p.bw : tid < FD + FH ? p.bw : 1);
@@ -133,7 +103,7 @@ __device__ __forceinline__ void up_from_box(const UpTileParams& p, const unsigne
 template <typename T, int MODE>
 __global__ void __launch_bounds__(UT) k_up_tile(UpTileParams p) {
   constexpr int CPC = Elem<T>::CPC;
-  UT_DYN_SMEM(smem);
+  CBIM_DYN_SMEM(smem);
   const int tid = threadIdx.x, n = blockIdx.y;
   const int Ct = MODE == 0 ? p.Cl : p.Cs + p.Cl;
   const int cch = Ct / CPC, vlc = UT / cch;
@@ -142,7 +112,7 @@ __global__ void __launch_bounds__(UT) k_up_tile(UpTileParams p) {
   const int skip_lo = p.skip_first ? 0 : p.Cl, low_lo = MODE == 0 ? 0 : (p.skip_first ? p.Cs : 0);
   const int c0 = cc * CPC;
   const bool is_skip = MODE != 0 && c0 >= skip_lo && c0 < skip_lo + p.Cs;
-  const float sd = ulin_scale(p.Dl, p.D), sh = ulin_scale(p.Hl, p.H), sw = ulin_scale(p.Wl, p.W);
+  const float sd = lin_scale(p.Dl, p.D), sh = lin_scale(p.Hl, p.H), sw = lin_scale(p.Wl, p.W);
   float mean[CPC], rstd[CPC], m1[CPC], m2[CPC];
   float s0[CPC], s1[CPC], shift[CPC];
   float cnt = 0.f;
@@ -188,12 +158,12 @@ __global__ void __launch_bounds__(UT) k_up_tile(UpTileParams p) {
         fwv[b] = v % FW; fhv[b] = (v / FW) % FH; fdv[b] = v / (FW * FH);
         const int d = td * FD + fdv[b], h = th * FH + fhv[b], w = tw * FW + fwv[b];
         ok[b] = v < FV && d < p.D && h < p.H && w < p.W;
-        vox[b] = ut_mad24(ut_mad24((unsigned)d, (unsigned)p.H, (unsigned)h), (unsigned)p.W, (unsigned)w);
+        vox[b] = umad24(umad24((unsigned)d, (unsigned)p.H, (unsigned)h), (unsigned)p.W, (unsigned)w);
         sk[b] = u32x4{0u, 0u, 0u, 0u};
         gq[b] = u32x4{0u, 0u, 0u, 0u};
         if (ok[b]) {
-          if (is_skip) sk[b] = *(const u32x4*)(skip_n + ut_mad24(vox[b], skip_rb, skip_cb));
-          if (MODE == 2) gq[b] = *(const u32x4*)(g_n + ut_mad24(vox[b], cat_rb, cat_cb));
+          if (is_skip) sk[b] = *(const u32x4*)(skip_n + umad24(vox[b], skip_rb, skip_cb));
+          if (MODE == 2) gq[b] = *(const u32x4*)(g_n + umad24(vox[b], cat_rb, cat_cb));
         }
       }
 #pragma unroll
@@ -218,7 +188,7 @@ __global__ void __launch_bounds__(UT) k_up_tile(UpTileParams p) {
 #pragma unroll
             for (int j = 0; j < CPC; ++j) f[j] = act_fwd((f[j] - mean[j]) * rstd[j], p.act);
           }
-          *(u32x4*)(out_n + ut_mad24(vox[b], cat_rb, cat_cb)) = Elem<T>::pack(f);
+          *(u32x4*)(out_n + umad24(vox[b], cat_rb, cat_cb)) = Elem<T>::pack(f);
         } else {
           float gg[CPC];
           Elem<T>::unpack(gq[b], gg);
@@ -227,8 +197,8 @@ __global__ void __launch_bounds__(UT) k_up_tile(UpTileParams p) {
             const float xh = (f[j] - mean[j]) * rstd[j];
             gg[j] = rstd[j] * (gg[j] - m1[j] - xh * m2[j]);
           }
-          if (is_skip) *(u32x4*)(out_n + ut_mad24(vox[b], skip_rb, skip_cb)) = Elem<T>::pack(gg);
-          else *(u32x4*)(out2_n + ut_mad24(vox[b], low_rb, low_cb)) = Elem<T>::pack(gg);
+          if (is_skip) *(u32x4*)(out_n + umad24(vox[b], skip_rb, skip_cb)) = Elem<T>::pack(gg);
+          else *(u32x4*)(out2_n + umad24(vox[b], low_rb, low_cb)) = Elem<T>::pack(gg);
         }
       }
     }
