@@ -166,6 +166,8 @@ _SIGS = {
     "cbim_softmax_accumulate": (i32, [vp, vp, vp] + [i32] * 11 + [vp]),
     "cbim_prob_finalize": (i32, [vp, vp, vp, i32, i32, i64, vp]),
     "cbim_dice_counts": (i32, [vp, i32, vp, i32, i64, i64, i32, vp, vp]),
+    "cbim_window_gather_mirror": (i32, [vp, vp, C.POINTER(C.c_int), i32] + [i32] * 11 + [vp]),
+    "cbim_softmax_accumulate_tta": (i32, [vp, C.POINTER(C.c_int), i32, vp, vp, vp, vp, vp] + [i32] * 11 + [vp]),
     "cbim_surface_scan": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp]),
     "cbim_surface_lists": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, i64, f64, f64, f64, vp, vp, vp, vp, vp, i64, vp, vp]),
     "cbim_order_stats_workspace": (sz, []),

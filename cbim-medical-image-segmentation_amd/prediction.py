@@ -44,7 +44,10 @@ def prediction(model_list, tensor_img, args, return_total=False):
     """Ensemble prediction of one preprocessed volume [D, H, W] (prediction.py:35-62): every model's window-averaged
     probabilities are summed in list order in float32 and the first maximum over the classes is the label.  The sliding-window
     accumulators feed the ensemble kernel directly; no model's probabilities are written out on their own.  The compute dtype is
-    the engine's (``cbim_amd.set_compute_dtype``).  Returns uint8 [D, H, W] (with return_total also the summed probabilities)."""
+    the engine's (``cbim_amd.set_compute_dtype``).  The optional keys args.tta_mirror_axes, args.window_weight,
+    args.window_sigma_scale and args.tta_batch (mirror test-time augmentation and Gaussian window weights, see
+    inference/inference3d.py) apply to every model; the count handed to the ensemble kernel is then the sum of weights.
+    Returns uint8 [D, H, W] (with return_total also the summed probabilities)."""
     _check_dim(args)
     get_inference(args)
     inference3d._label_gate()
@@ -64,7 +67,7 @@ def prediction(model_list, tensor_img, args, return_total=False):
                 acc, counter, _ = inference3d._sliding_window_accumulate(model, x, args)
                 acc, counter = acc[0], counter[0, 0]
             else:
-                acc, counter = inference3d.inference_whole_image(model, x)[0], None
+                acc, counter = inference3d.inference_whole_image(model, x, args)[0], None    # under TTA already the variant mean
             if total is None and (M > 1 or return_total):
                 total = torch.empty_like(acc)
             if labels is None:

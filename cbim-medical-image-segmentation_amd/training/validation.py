@@ -5,6 +5,9 @@ the class.  Forward, argmax, Dice counts and the surface distances run on the de
 The surfel-area table of the distance metrics is an input (``metric.utils.calculate_distance``): ``args.area_table`` when the
 caller sets it (256 values or a callable spacing -> table), else ``metric.lookup_tables`` of the host project.
 No progress bar and no SimpleITK: neither is part of the computation.
+
+Mirror test-time augmentation and Gaussian window weights are switched on through ``args`` (tta_mirror_axes, window_weight,
+window_sigma_scale, tta_batch: see inference/inference3d.py); both loops pick them up through ``get_inference(args)``.
 """
 import logging
 

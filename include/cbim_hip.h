@@ -586,6 +586,29 @@ int cbim_prob_finalize(float* prob_sum, const float* counter, int64_t* labels, i
 int cbim_dice_counts(const void* pred, int pred_bytes, const void* target, int target_bytes, int64_t N,
                      int64_t block, int C, int32_t* counts, void* stream);
 
+/* Mirror test-time augmentation and separable window weights for the window tail above (no counterpart in the reference,
+ * whose windows count 1 everywhere and get one forward each; composed from torch they are a slice + .contiguous() + V
+ * torch.flip of the input, V torch.flip of the logits, V cbim_softmax_accumulate into a temporary and a multiply-add).
+ * A flip code is 3 bits: bit 0 reverses D, bit 1 H, bit 2 W.  `codes` is a HOST array of V codes, 1 <= V <= 8, each 0..7,
+ * read before the launch (not retained); anything else returns CBIM_EINVAL, as does a window outside the volume.
+ *   cbim_window_gather_mirror   : replaces img[:, :, d0:d0+wd, h0:h0+wh, w0:w0+ww].contiguous() and the V flips:
+ *                                 out[v*B + b][c][z][y][x] = img[b][c][d0 + fz][h0 + fy][w0 + fx], f* = n-1-* on the axes
+ *                                 code v reverses; img [B][C][D][H][W], out [V*B][C][wd][wh][ww], float32; a pure copy
+ *   cbim_softmax_accumulate_tta : replaces V x (flip back + cbim_softmax_accumulate) + the weight multiply-add:
+ *                                 logits [V*B][K][wd][wh][ww] in the layout above; per window voxel (b, z, y, x) in
+ *                                 UN-mirrored coordinates s_k = sum over v = 0..V-1, in that order, of softmax_k of
+ *                                 variant v's logits at the mirrored position (the arithmetic of cbim_softmax_accumulate);
+ *                                 then prob_sum_k += w * s_k and wsum += w * V with w = (wz[z] * wy[y]) * wx[x] in
+ *                                 float32.  wz [wd], wy [wh], wx [ww] are device vectors, all three or none; none: no
+ *                                 multiply at all.  wsum [B][1][D][H][W] may be NULL.  No atomics, fixed order: bitwise
+ *                                 reproducible; with V = 1, code 0 and no weights bit-identical to
+ *                                 cbim_softmax_accumulate.  cbim_prob_finalize / cbim_ensemble_finalize divide by wsum. */
+int cbim_window_gather_mirror(const float* img, float* out, const int* codes, int V, int B, int C, int wd, int wh, int ww,
+                              int D, int H, int W, int d0, int h0, int w0, void* stream);
+int cbim_softmax_accumulate_tta(const float* logits, const int* codes, int V, const float* wz, const float* wy,
+                                const float* wx, float* prob_sum, float* wsum, int B, int K, int wd, int wh, int ww, int D,
+                                int H, int W, int d0, int h0, int w0, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Surface-distance metrics (ASD / HD95) — the reference's metric/metrics.py compute_surface_distances for every
  * foreground class of two label volumes [D][H][W] (int8 or int64), csrc/surface_kernels.hip.

@@ -1,0 +1,56 @@
+"""CPU suite: mirror test-time augmentation and Gaussian window weights on the host-side executor — the kernels
+cbim_window_gather_mirror / cbim_softmax_accumulate_tta of csrc/inference_kernels.hip and the args keys of
+cbim_amd.inference.inference3d (checks in tests/tta_checks.py; the -m gpu twin is tests/test_gpu_tta.py)."""
+import pytest
+
+from tests import tta_checks as tc
+
+
+@pytest.fixture(autouse=True)
+def _emu_only(dev):
+    if dev != "cpu":
+        pytest.skip("CPU suite (the -m gpu twin is tests/test_gpu_tta.py)")
+
+
+def test_gather_equals_flipped_slice(dev):
+    tc.check_gather(dev)
+
+
+def test_single_variant_is_bit_identical_to_softmax_accumulate(dev):
+    tc.check_bit_identity(dev)
+
+
+def test_accumulate_against_float64_composition(dev):
+    tc.check_against_float64(dev)
+
+
+def test_accumulate_is_reproducible(dev):
+    tc.check_reproducible(dev)
+
+
+def test_argument_errors(dev):
+    tc.check_argument_errors(dev)
+
+
+def test_mirror_equivariance_whole_image(dev):
+    tc.check_mirror_equivariance(dev)
+
+
+def test_sliding_window_against_whole_image_composition(dev):
+    tc.check_sliding_window_tta(dev)
+
+
+def test_defaults_are_the_old_path(dev):
+    tc.check_defaults_are_the_old_path(dev)
+
+
+def test_prediction_and_validation_pick_the_keys_up(dev):
+    tc.check_consumers(dev)
+
+
+def test_host_logic():
+    tc.check_host_logic()
+
+
+def test_key_errors_before_any_launch(dev):
+    tc.check_key_errors_before_any_launch(dev)

@@ -7,7 +7,16 @@ bytes (percentile: 4 passes over the volume; prefilter: 3 axes x 2 sweeps x read
 write; ensemble tail: prob_sum + total read, total written, labels written; label resample: read + write of 1-byte labels).
 `non_network_share`: everything but the models' sliding windows, as a share of the whole.  `stock`: the same stage written with
 stock torch on the same box in the same process (torch.quantile is limited to 16M elements, so kthvalue stands in for it).
---scipy adds the CPU time of scipy's cubic resample of the same volume, for scale."""
+--scipy adds the CPU time of scipy's cubic resample of the same volume, for scale.
+
+    python tools/bench_prediction.py --tta [--reps 5] [--out profiles/tta.json] [--no-volume]
+times the window tail of ONE 128^3, 16-class window under 8 mirror variants + Gaussian window weights, without the network:
+(a) cbim_window_gather_mirror + cbim_softmax_accumulate_tta; (b) the same result composed from what the engine had before them:
+slice + .contiguous(), 8 x torch.flip of the input, 8 x torch.flip of the logits, 8 x cbim_softmax_accumulate into a temporary, a
+torch multiply-add by the weight volume.  Both in the same process, alternating, each sample a loop of --inner calls between two
+device events; the results are compared first.  Algorithmic bytes of (a): V*(2 + K) + 2*K + 2 + 1 floats per window voxel.  Unless
+--no-volume, also the sliding-window time of one model over the whole resampled volume with TTA off and on (information only).
+The JSON line is also written to --out with the device name and the date."""
 import argparse
 import json
 import os
@@ -48,7 +57,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--scipy", action="store_true")
+    ap.add_argument("--tta", action="store_true", help="only the mirror-TTA / Gaussian window tail stage")
+    ap.add_argument("--inner", type=int, default=10)
+    ap.add_argument("--no-volume", action="store_true")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "tta.json"))
     a = ap.parse_args()
+    if a.tta:
+        return tta_stage(a)
     from cbim_amd.model.dim3 import UNet
     dev = torch.device("cuda")
     rng = np.random.default_rng(11)
@@ -126,6 +141,97 @@ def main():
         ndimage.map_coordinates(raw, rs.map_coordinates_zyx(m, out_shape), order=3, mode="mirror", output=np.float32)
         out["scipy_cubic_resample_cpu_s"] = time.perf_counter() - t0
     print(json.dumps(out))
+
+
+def tta_stage(a):
+    import datetime
+    dev = torch.device("cuda")
+    V, K, win, vol, origin = 8, CLASSES, tuple(WINDOW), (160, 256, 256), (16, 64, 96)
+    codes = inference3d.mirror_variants((0, 1, 2))
+    weights = inference3d.window_weights(win, "gaussian", 0.125, dev)
+    w3 = (weights[0][:, None, None] * weights[1][None, :, None]) * weights[2][None, None, :]
+    gen = torch.Generator(device="cuda").manual_seed(3)
+    img = torch.randn((1, 1) + vol, device=dev, generator=gen)
+    logits = torch.randn((V, K) + win, device=dev, generator=gen) * 3
+    d0, h0, w0 = origin
+    sl = (slice(None), slice(None), slice(d0, d0 + win[0]), slice(h0, h0 + win[1]), slice(w0, w0 + win[2]))
+    dims = [[2 + ax for ax in range(3) if c >> ax & 1] for c in codes]
+    tmp = torch.empty((1, K) + win, device=dev)
+
+    def new(acc, wsum):
+        x = inference3d._gather_mirror(img, codes, d0, h0, w0, win)
+        inference3d._accumulate_tta(logits, codes, weights, acc, wsum, d0, h0, w0)
+        return x
+
+    def composed(acc, wsum):
+        w = img[sl].contiguous()
+        x = torch.cat([torch.flip(w, d) if d else w for d in dims])
+        tmp.zero_()
+        for v, d in enumerate(dims):
+            lv = logits[v:v + 1]
+            inference3d._accumulate(torch.flip(lv, d) if d else lv, tmp, None, 0, 0, 0)
+        acc[sl] += w3 * tmp
+        wsum[sl] += w3 * float(V)
+        return x
+
+    outs = []
+    for fn in (new, composed):                       # same result first (reordered float32 sums: last bits only)
+        acc, wsum = torch.zeros((1, K) + vol, device=dev), torch.zeros((1, 1) + vol, device=dev)
+        x = fn(acc, wsum)
+        outs.append((x, acc, wsum))
+    assert torch.equal(outs[0][0], outs[1][0])
+    d_acc = float((outs[0][1] - outs[1][1]).abs().max())
+    d_ws = float(((outs[0][2] - outs[1][2]).abs() / outs[1][2].clamp_min(1e-30)).max())
+    assert d_acc < 8 * 2.0 ** -20 and d_ws < 1e-6, (d_acc, d_ws)
+    acc, wsum = outs[0][1], outs[0][2]
+    ms = {"new": [], "composed": []}
+    for it in range(a.reps + 1):                      # alternating; the first round is warm-up
+        for name, fn in (("new", new), ("composed", composed)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(a.inner):
+                fn(acc, wsum)
+            e1.record()
+            torch.cuda.synchronize()
+            if it:
+                ms[name].append(e0.elapsed_time(e1) / a.inner)
+    t_new, t_old = statistics.median(ms["new"]), statistics.median(ms["composed"])
+    nvox = win[0] * win[1] * win[2]
+    floats = V * (2 + K) + 2 * K + 2 + 1
+    out = {"bench": "tta_window_tail", "device": torch.cuda.get_device_name(0), "date": datetime.date.today().isoformat(),
+           "window": list(win), "classes": K, "variants": V, "window_weight": "gaussian", "reps": a.reps, "inner": a.inner,
+           "new_ms": t_new, "composed_ms": t_old, "ratio": t_old / t_new, "new_ms_all": ms["new"], "composed_ms_all": ms["composed"],
+           "new_algorithmic_gbs": floats * 4 * nvox / t_new / 1e6, "max_abs_diff_acc": d_acc}
+    del outs, acc, wsum, logits, tmp
+    if not a.no_volume:
+        out["volume"] = tta_volume()
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+def tta_volume():
+    """information only: one model's sliding windows over the resampled 400x256x256 volume, bf16, TTA + Gaussian off and on"""
+    from cbim_amd.model.dim3 import UNet
+    dev = torch.device("cuda")
+    shape = rs.resampled_size(SHAPE, SPACING, TARGET)
+    x = torch.rand((1, 1) + tuple(shape), device=dev)
+    torch.manual_seed(0)
+    net = UNet(1, 32, scale=[[2, 2, 2]] * 4, kernel_size=[[3, 3, 3]] * 5, num_classes=CLASSES, block="BasicBlock", norm="in").to(dev)
+    base = dict(dimension="3d", classes=CLASSES, window_size=WINDOW, sliding_window=True)
+    on = dict(base, tta_mirror_axes=(0, 1, 2), window_weight="gaussian", tta_batch=1)
+    cbim_amd.set_compute_dtype("bf16")
+    try:
+        res = {"shape": list(shape), "tta_batch": 1}
+        for name, kw in (("off_ms", base), ("on_ms", on)):
+            res[name], _ = timed(lambda: inference3d.inference_sliding_window(net, x, argparse.Namespace(**kw)), 1)
+    finally:
+        cbim_amd.set_compute_dtype(None)
+    res["on_over_off"] = res["on_ms"] / res["off_ms"]
+    return res
 
 
 def _cubic(lib, coef, m, out_shape, st):
