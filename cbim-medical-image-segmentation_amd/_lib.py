@@ -175,6 +175,7 @@ _SIGS = {
     "cbim_bspline3_prefilter": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "cbim_resample3d": (i32, [i32, vp, vp, i32] + [i32] * 7 + [IndexMap, C.c_uint32, vp]),
     "cbim_ensemble_finalize": (i32, [vp, vp, vp, vp, i32, i64, i32, i32, vp]),
+    "cbim_resample_argmax": (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(C.c_int), vp, i32, i32, i32, IndexMap, vp]),
     "cbim_components_workspace_bytes": (i64, [i32, i32, i32]),
     "cbim_components_label": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "cbim_components_sizes": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),

@@ -13,6 +13,9 @@
 //                           (bit copy) / linear (edge-clamped) / cubic (4x4x4 taps on the coefficients, mirrored indices)
 //   k_ensemble_finalize     p = prob_sum / counter; total = first ? p : total + p; on the last model the first maximum over
 //                           classes as uint8 — one pass per model
+//   k_resample_argmax       class probabilities straight to the label map on another grid: per output voxel the taps and weights of
+//                           k_resample3d<LINEAR> once, then per class the same trilinear sum (each tap optionally divided by the
+//                           window count) and a running first maximum — the K resampled volumes are never written
 #include "cbim_common.h"
 
 #include <string.h>
@@ -319,6 +322,75 @@ __global__ void __launch_bounds__(PR_T) k_ensemble_finalize(const float* __restr
   }
 }
 
+// ---- probabilities -> label map on another grid ------------------------------------------------------------------------------------
+// What resample3d(linear) over the K channels of prob / counter followed by the first maximum gives, with no [K][Do][Ho][Wo]
+// volume in between.  prob and counter point at the first sample of the crop box; sz, sy are the BUFFER's plane and row pitch, Sb
+// its channel pitch; Dc, Hc, Wc the box: inside test and clamps see only the box, like resample3d on the sliced-out copy.
+// A workgroup owns a box of 64 x 2 x 2 outputs (a wave = 64 neighbours along x): under up-sampling its outputs share source rows
+// and planes, so per class the box touches a few hundred bytes that stay in the L1 from the first tap to the last, and the
+// channel loop walks K such footprints one channel pitch apart.  Tiles are dealt so that neighbouring ones share an XCD's L2.
+static constexpr int RA_TX = 64, RA_TY = 2, RA_TZ = 2;
+static_assert(RA_TX * RA_TY * RA_TZ == PR_T, "one output voxel per thread");
+
+template <bool COUNTER>
+__global__ void __launch_bounds__(PR_T) k_resample_argmax(const float* __restrict__ prob, const float* __restrict__ counter,
+                                                          uint8_t* __restrict__ labels, int K, int64_t Sb, int64_t sz, int64_t sy,
+                                                          int Dc, int Hc, int Wc, int Do, int Ho, int Wo, int ntx, int nty,
+                                                          int64_t tiles, cbim_index_map map) {
+  const double* m = map.m;
+  const int lx = threadIdx.x % RA_TX, ly = (threadIdx.x / RA_TX) % RA_TY, lz = threadIdx.x / (RA_TX * RA_TY);
+  for (int64_t t = xcd_remap(blockIdx.x, gridDim.x); t < tiles; t += gridDim.x) {
+    const int i = (int)(t % ntx) * RA_TX + lx, j = (int)((t / ntx) % nty) * RA_TY + ly, k = (int)(t / ((int64_t)ntx * nty)) * RA_TZ + lz;
+    if (i >= Wo || j >= Ho || k >= Do) continue;
+    uint8_t* out = labels + ((int64_t)k * Ho + j) * Wo + i;
+    const double cz = ((m[0] * k + m[1] * j) + m[2] * i) + m[3];
+    const double cy = ((m[4] * k + m[5] * j) + m[6] * i) + m[7];
+    const double cx = ((m[8] * k + m[9] * j) + m[10] * i) + m[11];
+    const bool in = cz >= -0.5 && cz < Dc - 0.5 && cy >= -0.5 && cy < Hc - 0.5 && cx >= -0.5 && cx < Wc - 0.5;
+    if (!in) { *out = 0; continue; }
+    const double fz = floor(cz), fy = floor(cy), fx = floor(cx);
+    const int bz = (int)fz, by = (int)fy, bx = (int)fx;
+    const float tz = (float)(cz - fz), ty = (float)(cy - fy), tx = (float)(cx - fx);
+    const float wz[2] = {1.f - tz, tz}, wy[2] = {1.f - ty, ty}, wx[2] = {1.f - tx, tx};
+    const int ix[2] = {rs_clamp(bx, Wc), rs_clamp(bx + 1, Wc)};
+    int64_t ro[2][2];                                            // row starts inside one channel, shared by all K classes
+    float cv[2][2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        ro[a][b] = (int64_t)rs_clamp(bz + a, Dc) * sz + (int64_t)rs_clamp(by + b, Hc) * sy;
+        if constexpr (COUNTER) { cv[a][b][0] = counter[ro[a][b] + ix[0]]; cv[a][b][1] = counter[ro[a][b] + ix[1]]; }
+      }
+    float best = -INFINITY;
+    int arg = 0;
+    const float* pk = prob;
+#pragma unroll 2
+    for (int c = 0; c < K; ++c, pk += Sb) {
+      float acc = 0.f;
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        float plane = 0.f;
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          const float* rp = pk + ro[a][b];
+          float row = 0.f;
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            float v = rp[ix[e]];
+            if constexpr (COUNTER) v = v / cv[a][b][e];          // the division of k_ensemble_finalize, per tap
+            row += wx[e] * v;
+          }
+          plane += wy[b] * row;
+        }
+        acc += wz[a] * plane;
+      }
+      if (acc > best) { best = acc; arg = c; }                   // first maximum
+    }
+    *out = (uint8_t)arg;
+  }
+}
+
 static inline int pr_grid(int64_t items, int per_block, int cap) {
   int64_t b = (items + per_block - 1) / per_block;
   if (b > cap) b = cap;
@@ -419,6 +491,30 @@ extern "C" int cbim_ensemble_finalize(const float* prob_sum, const float* counte
   CBIM_CHECK(total != prob_sum, CBIM_EINVAL, "ensemble_finalize: total must not alias prob_sum");
   CBIM_LAUNCH(k_ensemble_finalize, dim3(pr_grid(S, PR_T, 1 << 16)), dim3(PR_T), 0, (hipStream_t)stream, prob_sum, counter, total, labels, K,
               S, first, last);
+  PR_LAUNCHED();
+  return CBIM_OK;
+}
+
+extern "C" int cbim_resample_argmax(const float* prob, const float* counter, int K, int Db, int Hb, int Wb, const int* crop,
+                                    uint8_t* labels, int Do, int Ho, int Wo, cbim_index_map map, void* stream) {
+  CBIM_CHECK(prob && crop && labels, CBIM_EINVAL, "resample_argmax: null pointer");
+  CBIM_CHECK(K >= 1 && K <= 256, CBIM_EINVAL, "resample_argmax: %d classes, the label is one byte (1..256)", K);
+  CBIM_CHECK(Db >= 1 && Hb >= 1 && Wb >= 1 && Do >= 1 && Ho >= 1 && Wo >= 1, CBIM_EINVAL, "resample_argmax: bad extents");
+  const int z0 = crop[0], z1 = crop[1], y0 = crop[2], y1 = crop[3], x0 = crop[4], x1 = crop[5];
+  CBIM_CHECK(0 <= z0 && z0 < z1 && z1 <= Db && 0 <= y0 && y0 < y1 && y1 <= Hb && 0 <= x0 && x0 < x1 && x1 <= Wb, CBIM_EINVAL,
+             "resample_argmax: crop [%d:%d, %d:%d, %d:%d] is empty or outside the buffer [%d, %d, %d]", z0, z1, y0, y1, x0, x1, Db, Hb, Wb);
+  for (int a = 0; a < 12; ++a) CBIM_CHECK(map.m[a] == map.m[a] && fabs(map.m[a]) < 1e15, CBIM_EINVAL, "resample_argmax: index map entry %d is not finite", a);
+  const int64_t sy = Wb, sz = (int64_t)Hb * Wb, Sb = (int64_t)Db * sz, first = (int64_t)z0 * sz + (int64_t)y0 * sy + x0;
+  const int ntx = (Wo + RA_TX - 1) / RA_TX, nty = (Ho + RA_TY - 1) / RA_TY, ntz = (Do + RA_TZ - 1) / RA_TZ;
+  const int64_t tiles = (int64_t)ntx * nty * ntz;
+  const dim3 grid(pr_grid(tiles, 1, 1 << 22)), block(PR_T);
+  hipStream_t st = (hipStream_t)stream;
+  if (counter)
+    CBIM_LAUNCH(k_resample_argmax<true>, grid, block, 0, st, prob + first, counter + first, labels, K, Sb, sz, sy, z1 - z0, y1 - y0, x1 - x0,
+                Do, Ho, Wo, ntx, nty, tiles, map);
+  else
+    CBIM_LAUNCH(k_resample_argmax<false>, grid, block, 0, st, prob + first, counter, labels, K, Sb, sz, sy, z1 - z0, y1 - y0, x1 - x0, Do,
+                Ho, Wo, ntx, nty, tiles, map);
   PR_LAUNCHED();
   return CBIM_OK;
 }

@@ -113,6 +113,71 @@ def resample_label_to_ref(label, label_geom, ref_geom, ref_shape):
     return resample3d(label, index_map(label_geom, ref_geom), ref_shape, "nearest")
 
 
+def _buffer_box(t):
+    """(Db, Hb, Wb) of the contiguous [.., Db, Hb, Wb] buffer that t [.., D, H, W] is a leading corner of (t itself when
+    contiguous; a view such as ``total[:, :D, :H, :W]``), or None when its strides are not those of such a corner."""
+    *lead, D, H, W = (int(v) for v in t.shape)
+    if t.is_contiguous():
+        return (D, H, W)
+    st = [int(v) for v in t.stride()]
+    sz, sy, sx = st[-3:]
+    if sx != 1 or sy < W or sz < sy * H or sz % sy:
+        return None
+    box = (D, sz // sy, sy)
+    if lead:
+        if len(lead) != 1 or (lead[0] > 1 and (st[0] < sz * D or st[0] % sz)):
+            return None
+        if lead[0] > 1:
+            box = (st[0] // sz, sz // sy, sy)
+    return box
+
+
+def resample_argmax(prob, m, out_shape, counter=None, crop=None):
+    """The label map of class probabilities on another grid: prob float32 [K, D, H, W] (K <= 256) interpolated trilinearly onto
+    out_shape (z, y, x) through the index map m, first maximum over the classes, 0 outside — argmax(resample3d(prob, m,
+    out_shape, 'linear'), 0) in one kernel that never writes the K resampled volumes.  counter float32 [D, H, W]: the window
+    count the sliding-window sums are still to be divided by (each tap is prob / counter, the labels are those of the
+    materialised quotient).  crop (z0, z1, y0, y1, x0, x1): the box of the buffer that is the image — m maps into the box,
+    the edge clamps stay inside it: the result of ``prob[:, z0:z1, y0:y1, x0:x1]`` without the copy.  A prob that is itself a
+    leading corner of a larger contiguous buffer (``total[:, :D, :H, :W]``) is read in place.  Returns uint8 [*out_shape]."""
+    prob = torch.as_tensor(prob)
+    if prob.dim() != 4:
+        raise NotImplementedError("cbim_amd: resample_argmax takes class probabilities [K, D, H, W]")
+    if prob.dtype != torch.float32 or (counter is not None and torch.as_tensor(counter).dtype != torch.float32):
+        raise TypeError("cbim_amd: resample_argmax takes float32 probabilities and counts")
+    dev = _device(prob)
+    prob = prob.to(dev)
+    K, D, H, W = map(int, prob.shape)
+    if counter is not None:
+        counter = torch.as_tensor(counter).to(dev)
+        if tuple(counter.shape) != (D, H, W):
+            raise ValueError(f"cbim_amd: counter {tuple(counter.shape)} does not match the probabilities {tuple(prob.shape)}")
+    box = _buffer_box(prob)
+    if box is None or (counter is not None and (_buffer_box(counter) or (0, 0, 0))[1:] != box[1:]):
+        prob, box = prob.contiguous(), (D, H, W)
+        counter = None if counter is None else counter.contiguous()
+    crop = (0, D, 0, H, 0, W) if crop is None else tuple(int(v) for v in crop)
+    if len(crop) != 6:
+        raise ValueError("cbim_amd: crop is (z0, z1, y0, y1, x0, x1)")
+    if box != (D, H, W) and any(hi > n for hi, n in zip(crop[1::2], (D, H, W))):
+        raise ValueError(f"cbim_amd: crop {crop} leaves the view {(D, H, W)}")
+    Do, Ho, Wo = map(int, out_shape)
+    labels = torch.empty((Do, Ho, Wo), dtype=torch.uint8, device=dev)
+    _dev_ok(labels)                                           # prob and counter sit on the same device, possibly as corner views
+    im = _lib.IndexMap()
+    im.m[:] = [float(v) for v in np.asarray(m, np.float64).reshape(12)]
+    _lib.check(_lib.lib().cbim_resample_argmax(_p(prob), _p(counter), K, box[0], box[1], box[2], (C.c_int * 6)(*crop), _p(labels),
+                                               Do, Ho, Wo, im, _stream(prob)), "resample_argmax")
+    return labels
+
+
+def resample_probabilities_to_ref(prob, geom, ref_geom, ref_shape, counter=None, crop=None):
+    """The probability twin of resample_label_to_ref: class probabilities [K, D, H, W] on the grid `geom` (that of the crop box
+    when crop is given) -> the uint8 label map on the reference image's grid, by trilinear interpolation of every class and
+    the first maximum there (the nnU-Net rule); 0 outside.  Same index map as the label path."""
+    return resample_argmax(prob, index_map(geom, ref_geom), ref_shape, counter=counter, crop=crop)
+
+
 def order_stats(t, ranks):
     """The values at the given 0-based ranks (at most 4) of the ascending order of the float32 tensor t, as a numpy float32
     array: one readback of len(ranks) floats.  t must not hold NaN."""

@@ -16,7 +16,8 @@ import torch.nn.functional as F
 from . import _lib
 from .inference import inference3d
 from .inference.components import filter_components
-from .inference.resample import IDENTITY, _device, percentile, resample_label_to_ref, resample_xyz_axis
+from .inference.resample import (IDENTITY, _device, percentile, resample_label_to_ref, resample_probabilities_to_ref,
+                                 resample_xyz_axis)
 from .inference.utils import get_inference
 from .model.utils import get_model
 from .ops import _dev_ok, _p, _stream
@@ -151,33 +152,67 @@ def _filter_components(label, components):
     return filter_components(label.contiguous(), **components)
 
 
-def postprocess(label, original_idx, geom, ref_geom, ref_shape, args, components=None):
+def postprocess(label, original_idx, geom, ref_geom, ref_shape, args, components=None, probabilities=None, counter=None):
     """prediction.py:180-199: cut the padding off and, when the training spacing is not the scan's, bring the label map back onto
     the scan's grid by nearest neighbour.  geom: the geometry of the label map (None: args.target_spacing with the scan's origin
     and direction, as the reference sets it); ref_geom / ref_shape: the scan's.  components (not in the reference): None, or
     {"keep_largest": ..., "min_size": ..., "connectivity": ...} for ``inference.components.filter_components``, applied last, on
-    the scan's own grid.  Returns uint8 [*ref_shape] on the device."""
+    the scan's own grid.  probabilities (not in the reference): the class probabilities [K, D, H, W] of the padded volume
+    (``prediction(..., return_total=True)``, or the sliding-window sums with their ``counter`` [D, H, W]); when the spacings
+    differ the label map on the scan's grid is then the first maximum of the trilinearly interpolated probabilities
+    (``inference.resample.resample_probabilities_to_ref``, original_idx as its crop) and `label` may be None; with equal
+    spacings `label` — their argmax already — is used as always.  Returns uint8 [*ref_shape] on the device."""
     _check_dim(args)
-    label = unpad_img(torch.as_tensor(label).to(torch.uint8), original_idx, args)
     if geom is None:
         geom = (tuple(args.target_spacing), ref_geom[1], ref_geom[2])
-    if tuple(geom[0]) != tuple(ref_geom[0]):
-        label = resample_label_to_ref(label, geom, ref_geom, ref_shape)
+    if probabilities is not None and tuple(geom[0]) != tuple(ref_geom[0]):
+        label = resample_probabilities_to_ref(probabilities, geom, ref_geom, ref_shape, counter=counter, crop=original_idx)
+    else:
+        label = unpad_img(torch.as_tensor(label).to(torch.uint8), original_idx, args)
+        if tuple(geom[0]) != tuple(ref_geom[0]):
+            label = resample_label_to_ref(label, geom, ref_geom, ref_shape)
     if components is not None:
         label = _filter_components(label, components)
     return label
 
 
+def _window_sums(model, tensor_img, args):
+    """One model's probabilities of a preprocessed volume as prediction() hands them to the ensemble kernel: (sums [K, D, H, W],
+    window count [D, H, W] or None), both of the volume padded up to one window, not yet divided."""
+    _check_dim(args)
+    get_inference(args)
+    inference3d._label_gate()
+    img = torch.as_tensor(tensor_img)
+    x = img.to(_device(img)).float()[None, None].contiguous()
+    with torch.no_grad():
+        if args.sliding_window:
+            acc, counter, _ = inference3d._sliding_window_accumulate(model, x, args)
+            return acc[0], counter[0, 0]
+        return inference3d.inference_whole_image(model, x, args)[0], None
+
+
 def predict_volume(model_list, img, spacing, args, origin=(0.0, 0.0, 0.0), direction=IDENTITY, normalize="percentile",
-                   components=None):
+                   components=None, resample="nearest"):
     """The loop body of the reference's __main__ (prediction.py:277-286) for one raw scan: preprocess, prediction, postprocess.
     img float32 [D, H, W], spacing (x, y, z); args.target_spacing is the training spacing.  Returns the uint8 label map on the
-    scan's own grid, on the device; with ``components`` (see postprocess) after connected-component clean-up on that grid."""
+    scan's own grid, on the device; with ``components`` (see postprocess) after connected-component clean-up on that grid.
+    resample: how the result comes back onto the scan's grid when the spacings differ — 'nearest' (the reference: the label map
+    by nearest neighbour) or 'probabilities' (not in the reference: the class probabilities are interpolated trilinearly onto
+    the scan's grid and the argmax is taken there, in one kernel; a single model's sliding-window sums and counts go to it as
+    they are, an ensemble's through ``prediction(..., return_total=True)``)."""
+    if resample not in ("nearest", "probabilities"):
+        raise ValueError(f"predict_volume: resample is 'nearest' or 'probabilities', not {resample!r}")
     ref_geom = (tuple(spacing), tuple(origin), tuple(direction))
     ref_shape = tuple(int(v) for v in img.shape)
     tensor_img, original_idx = preprocess(img, spacing, args.target_spacing, args, normalize=normalize)
-    label = prediction(model_list, tensor_img, args)
-    return postprocess(label, original_idx, None, ref_geom, ref_shape, args, components=components)
+    if resample == "nearest" or tuple(args.target_spacing) == tuple(spacing):
+        label = prediction(model_list, tensor_img, args)
+        return postprocess(label, original_idx, None, ref_geom, ref_shape, args, components=components)
+    if len(model_list) == 1:
+        prob, counter = _window_sums(model_list[0], tensor_img, args)
+    else:
+        prob, counter = prediction(model_list, tensor_img, args, return_total=True)[1], None
+    return postprocess(None, original_idx, None, ref_geom, ref_shape, args, components=components, probabilities=prob, counter=counter)
 
 
 def init_model(args):

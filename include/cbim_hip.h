@@ -676,6 +676,18 @@ int cbim_surface_lists(const void* pred, int pred_bytes, const void* gt, int gt_
  *                          (prediction.py:57), and on the last model labels uint8 [S] = first maximum over the K <= 256
  *                          classes of total (torch.max, prediction.py:59).  prob_sum float [K][S] is not modified; counter
  *                          float [S]; total float [K][S] may be NULL only when first && last.
+ *   cbim_resample_argmax : labels uint8 [Do][Ho][Wo] = first maximum over the K <= 256 classes of the class probabilities
+ *                          interpolated onto the output grid — what cbim_resample3d(CBIM_RESAMPLE_LINEAR, default 0) over the K
+ *                          channels followed by the first maximum gives, without the [K][Do][Ho][Wo] volume.  prob float
+ *                          [K][Db][Hb][Wb]; counter float [Db][Hb][Wb] or NULL: a tap's value is prob[k][tap] / counter[tap], the
+ *                          division of cbim_ensemble_finalize, so the labels are those of the materialised quotient.  crop (HOST
+ *                          memory, 6 ints, read before the call returns) = (z0, z1, y0, y1, x0, x1), half-open, selects the box
+ *                          of the buffer that is the image: `map` gives the continuous index INSIDE the box (index 0 is z0), the
+ *                          inside test -0.5 <= c < n - 0.5 uses the box's extents and taps clamp to the box's first and last
+ *                          sample — the result is that of the sliced-out contiguous copy.  Arithmetic per class exactly that of
+ *                          CBIM_RESAMPLE_LINEAR (float64 coordinates, float32 fractions, x innermost, sequential float32 sums);
+ *                          a voxel outside the box is 0.  No atomics, no workspace: bitwise reproducible.  K outside 1..256, an
+ *                          empty crop or one outside the buffer, a non-finite map and NULL prob / crop / labels: CBIM_EINVAL.
  * ------------------------------------------------------------------------------------------ */
 #define CBIM_RESAMPLE_NEAREST 0
 #define CBIM_RESAMPLE_LINEAR 1
@@ -691,6 +703,8 @@ int cbim_resample3d(int mode, const void* src, void* dst, int elem_bytes, int C,
                     int Wo, cbim_index_map map, uint32_t default_bits, void* stream);
 int cbim_ensemble_finalize(const float* prob_sum, const float* counter, float* total, uint8_t* labels, int K, int64_t S,
                            int first, int last, void* stream);
+int cbim_resample_argmax(const float* prob, const float* counter, int K, int Db, int Hb, int Wb, const int* crop,
+                         uint8_t* labels, int Do, int Ho, int Wo, cbim_index_map map, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Connected components of a predicted label map and the clean-up built on them (csrc/components_kernels.hip).  The
