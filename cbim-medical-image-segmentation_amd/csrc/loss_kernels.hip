@@ -10,38 +10,9 @@
 //   den = TP + alpha*FP + (1-alpha)*FN = alpha*SP + (1-alpha)*CNT, dice = TP/(den+eps),
 //   L = mean_c(1-dice_c);  d L/d P_c(voxel) = dL/dTP_c * M_c + dL/dSP_c.
 // HBM-bound: logits are NCDHW fp32, one thread per voxel, coalesced plane reads.
-#include "cbim_common.h"
+#include "loss_common.h"   // VecF/ldv/stv, NT/CMAX/SMOOTH, loss_blocks/loss_vec, the finalize reduction, the per-class Dice term
 
 namespace cbim {
-
-static constexpr int NT = 256;
-static constexpr int CMAX = 32;
-static constexpr float SMOOTH = 1e-5f;
-
-// V consecutive voxels per thread: every class plane is read with one V*4-byte load per lane (16 B for V = 4, a
-// wave instruction then covers 1 KiB of one plane), labels as V int64.  CT = compile-time class bound (C <= CT) so
-// the per-class arrays live in registers without predicated dead work (C = 16 ran the CT = 32 loops before).
-template <int V> struct VecF;
-template <> struct VecF<4> { typedef f32x4 type; };
-template <> struct VecF<2> { typedef float type __attribute__((ext_vector_type(2))); };
-template <> struct VecF<1> { typedef float type; };
-template <int V> __device__ __forceinline__ void ldv(const float* p, float* o) {
-  typename VecF<V>::type q = *(const typename VecF<V>::type*)p;
-  if constexpr (V == 1) o[0] = q;
-  else {
-#pragma unroll
-    for (int i = 0; i < V; ++i) o[i] = q[i];
-  }
-}
-template <int V> __device__ __forceinline__ void stv(float* p, const float* o) {
-  typename VecF<V>::type q;
-  if constexpr (V == 1) q = o[0];
-  else {
-#pragma unroll
-    for (int i = 0; i < V; ++i) q[i] = o[i];
-  }
-  *(typename VecF<V>::type*)p = q;
-}
 
 // partial layout per workgroup: [3*C + 3] = TP[C], SP[C], CNT[C], ce_num, ce_den, #labels outside [0, C)
 // A label outside [0, C) (the reference raises in scatter_ / CrossEntropyLoss) is never used as an index: the voxel
@@ -131,47 +102,10 @@ __global__ void __launch_bounds__(NT) k_dice_ce_finalize(const float* __restrict
   __shared__ double part[4][3 * CMAX + 3];
   __shared__ double dice_term[CMAX];
   const int nv = 3 * C + 3;
-  {   // 4 thread groups stride over the workgroup partials (independent loads in flight), fixed-order merge
-    const int li = threadIdx.x & 63, pg = threadIdx.x >> 6;
-    for (int i = li; i < nv; i += 64) {
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;   // 4 loads in flight per trip
-      int b = pg;
-      for (; b + 12 < nblk; b += 16) {
-        a0 += (double)partials[(size_t)b * nv + i];
-        a1 += (double)partials[(size_t)(b + 4) * nv + i];
-        a2 += (double)partials[(size_t)(b + 8) * nv + i];
-        a3 += (double)partials[(size_t)(b + 12) * nv + i];
-      }
-      for (; b < nblk; b += 4) a0 += (double)partials[(size_t)b * nv + i];
-      part[pg][i] = (a0 + a1) + (a2 + a3);
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < nv; i += NT) tot[i] = (part[0][i] + part[1][i]) + (part[2][i] + part[3][i]);
-  __syncthreads();
+  loss_reduce_partials(partials, nblk, nv, tot, part);
   if ((int)threadIdx.x < C) {
     int c = threadIdx.x;
-    double TP = tot[c], SP = tot[C + c], CNT = tot[2 * C + c];
-    double eps = (double)SMOOTH;
-    double FP = SP - TP, FN = CNT - TP;
-    double T = FP + FN + eps;
-    double r = FP / T;
-    bool open = (r >= 0.2 && r <= 0.8);
-    double alpha = r < 0.2 ? 0.2 : (r > 0.8 ? 0.8 : r);
-    double den = TP + alpha * FP + (1.0 - alpha) * FN;
-    double dice = TP / (den + eps);
-    dice_term[c] = 1.0 - dice;
-    // d alpha / d TP, d alpha / d SP (only inside the clamp)
-    double da_dTP = open ? (FP - FN - eps) / (T * T) : 0.0;
-    double da_dSP = open ? (FN + eps) / (T * T) : 0.0;
-    double dden_dTP = (SP - CNT) * da_dTP;            // the explicit TP terms cancel
-    double dden_dSP = alpha + (SP - CNT) * da_dSP;
-    double q = TP / ((den + eps) * (den + eps));
-    double ddice_dTP = 1.0 / (den + eps) - q * dden_dTP;
-    double ddice_dSP = -q * dden_dSP;
-    coef[c] = (float)(-ddice_dTP / C);
-    coef[C + c] = (float)(-ddice_dSP / C);
-    coef[2 * C + 1 + c] = (float)(1.0 - dice);        // per-class loss term: DiceLoss(reduce=False) (losses.py:48-50)
+    dice_term[c] = dice_class_term(tot[c], tot[C + c], tot[2 * C + c], C, c, coef);
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -256,23 +190,6 @@ __global__ void __launch_bounds__(NT) k_dice_ce_bwd(const float* __restrict__ z,
         stv<V>(dp + (size_t)c * S, o);
       }
   }
-}
-
-static int loss_blocks(int64_t total) {
-  int64_t b = (total + NT * 8 - 1) / (NT * 8);   // upper bound over the vector widths (groups <= total)
-  // four workgroups per CU (16 waves: one 64-register wave per SIMD left the loads latency-bound, 55 us for 151 MB at
-  // 1x16x128^3); the single-workgroup finalize kernel walks these records, four independent loads per thread and trip
-  if (b > 1024) b = 1024;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-// voxels per thread: 4 (C <= 16) / 2 (C <= 32) consecutive voxels when every class plane stays aligned for the
-// vector load (S a multiple of V, base pointer aligned); otherwise one voxel per thread
-static int loss_vec(const void* logits, int64_t S, int C) {
-  const int V = C <= 16 ? 4 : 2;
-  if (S % V != 0 || ((size_t)logits % (V * 4)) != 0) return 1;
-  return V;
 }
 
 }  // namespace cbim

@@ -412,6 +412,29 @@ class HeadFn(torch.autograd.Function):
         return dx, (sw if sw is not None else dw.reshape(ctx.w_shape)), db
 
 
+def _count_bad_labels(out, logits):
+    """The out-of-range-label bookkeeping of a loss forward (out[3] of the loss kernels), shared by DiceCEFn and FocalFn."""
+    # out[3] = number of labels outside [0, C): the reference raises (scatter_ / CrossEntropyLoss); reading the
+    # count is a device synchronisation, so it is only checked on request
+    global _label_checks_left
+    capturing = logits.is_cuda and torch.cuda.is_current_stream_capturing()
+    want = _CHECK_LABELS == "1" or (_CHECK_LABELS not in ("", "0") and _label_checks_left > 0)
+    acc = _label_bad.get(logits.device)
+    if acc is None and not capturing and _CHECK_LABELS not in ("", "0"):
+        # the device-side count of out-of-range labels (functional.check_labels), allocated on the FIRST eager call so that it
+        # exists — outside any graph's private pool — before a training step is captured into a hipGraph
+        acc = _label_bad[logits.device] = torch.zeros(1, dtype=torch.float32, device=logits.device)
+    if want and not capturing:
+        _label_checks_left -= 1
+        bad = int(out[3].item())
+        if bad:
+            raise IndexError(f"cbim_amd: {bad} label(s) outside [0, {int(logits.shape[1])}) (Target out of bounds)")
+    elif acc is not None:
+        # unchecked call: keep the count on the device.  Under hipGraph capture the add is captured with the step, so every
+        # REPLAY keeps counting (the benchmarked mode); training.losses.check_labels() / the validation entry points read it
+        acc += out[3:4].detach()
+
+
 class DiceCEFn(torch.autograd.Function):
     """(CE, Dice, CE+Dice) of train.py:212 in one pass over the logits (training/losses.py:18-58)."""
 
@@ -422,25 +445,7 @@ class DiceCEFn(torch.autograd.Function):
         if labels.dtype != torch.int64:
             labels = labels.long()
         out, coef = ops.dice_ce_fwd(logits, labels, weight)
-        # out[3] = number of labels outside [0, C): the reference raises (scatter_ / CrossEntropyLoss); reading the
-        # count is a device synchronisation, so it is only checked on request
-        global _label_checks_left
-        capturing = logits.is_cuda and torch.cuda.is_current_stream_capturing()
-        want = _CHECK_LABELS == "1" or (_CHECK_LABELS not in ("", "0") and _label_checks_left > 0)
-        acc = _label_bad.get(logits.device)
-        if acc is None and not capturing and _CHECK_LABELS not in ("", "0"):
-            # the device-side count of out-of-range labels (functional.check_labels), allocated on the FIRST eager call so that it
-            # exists — outside any graph's private pool — before a training step is captured into a hipGraph
-            acc = _label_bad[logits.device] = torch.zeros(1, dtype=torch.float32, device=logits.device)
-        if want and not capturing:
-            _label_checks_left -= 1
-            bad = int(out[3].item())
-            if bad:
-                raise IndexError(f"cbim_amd: {bad} label(s) outside [0, {int(logits.shape[1])}) (Target out of bounds)")
-        elif acc is not None:
-            # unchecked call: keep the count on the device.  Under hipGraph capture the add is captured with the step, so every
-            # REPLAY keeps counting (the benchmarked mode); training.losses.check_labels() / the validation entry points read it
-            acc += out[3:4].detach()
+        _count_bad_labels(out, logits)
         ctx.save_for_backward(logits, labels, coef, weight if weight is not None else torch.empty(0))
         ctx.has_w = weight is not None
         return out
@@ -451,6 +456,38 @@ class DiceCEFn(torch.autograd.Function):
         g2 = torch.stack([gout[0] + gout[2], gout[1] + gout[2]]).float().contiguous()
         dz = ops.dice_ce_bwd(logits, labels, weight if ctx.has_w else None, coef, g2)
         return dz, None, None
+
+
+class FocalFn(torch.autograd.Function):
+    """(focal sum, focal mean, Dice, #bad labels, focal mean + Dice) of FocalLoss [+ DiceLoss] (training/losses.py:60-98, :8-58) in
+    one pass over the logits; labels [B, ...] or [B, 1, ...] (the kernels see [B][S] either way).  The Dice entry is 0 without
+    ``with_dice``."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, alpha, gamma, with_dice):
+        logits = logits.contiguous().float()
+        labels = labels.contiguous()
+        if labels.dtype != torch.int64:
+            labels = labels.long()
+        n_vox = logits.numel() // int(logits.shape[1])
+        if labels.numel() != n_vox:
+            raise ValueError(f"cbim_amd: {labels.numel()} labels for {n_vox} voxels")
+        out, coef = ops.focal_fwd(logits, labels, alpha, gamma, with_dice)
+        _count_bad_labels(out, logits)
+        empty = torch.empty(0)
+        ctx.save_for_backward(logits, labels, coef if coef is not None else empty, alpha if alpha is not None else empty)
+        ctx.has_a, ctx.gamma, ctx.with_dice, ctx.inv_count = alpha is not None, float(gamma), bool(with_dice), 1.0 / n_vox
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, labels, coef, alpha = ctx.saved_tensors
+        # (g_focal per voxel, g_dice) = (gout[0] + (gout[1] + gout[4]) / (N S), gout[2] + gout[4]) in two small launches
+        g2 = gout[1:3].float() + gout[4]
+        torch.add(gout[0], g2[0], alpha=ctx.inv_count, out=g2[0])
+        dz = ops.focal_bwd(logits, labels, alpha if ctx.has_a else None, coef if ctx.with_dice else None, g2, ctx.gamma,
+                           ctx.with_dice)
+        return dz, None, None, None, None
 
 
 class DicePerClassFn(torch.autograd.Function):

@@ -863,6 +863,33 @@ def dice_ce_bwd(logits, labels, weight, coef, grad2):
     return dz
 
 
+def focal_fwd(logits, labels, alpha=None, gamma=2.0, with_dice=False):
+    """-> out float32[5] = (focal sum, focal mean over N*S voxels, Dice (0 unless with_dice), #labels outside [0,C), mean + Dice),
+    coef: float32[3C+1] laid out as dice_ce_fwd's with with_dice, else None."""
+    _dev_ok(logits, labels, alpha)
+    N, Cc = int(logits.shape[0]), int(logits.shape[1])
+    S = logits.numel() // (N * Cc)
+    L = _lib.lib()
+    nbytes = L.cbim_focal_workspace(N, Cc, S)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=logits.device)
+    out = torch.empty((5,), dtype=torch.float32, device=logits.device)
+    coef = torch.empty((3 * Cc + 1,), dtype=torch.float32, device=logits.device) if with_dice else None
+    check(L.cbim_focal_fwd(_p(logits), _p(labels), _p(alpha), float(gamma), int(bool(with_dice)), N, Cc, S, _p(out), _p(coef),
+                           _p(ws), nbytes, _stream(logits)), "focal_fwd")
+    return out, coef
+
+
+def focal_bwd(logits, labels, alpha, coef, grad2, gamma=2.0, with_dice=False):
+    """grad2 float32[2] on the device: the gradient per voxel of the focal SUM (a mean's 1/(N*S) folded in) and of the Dice term."""
+    _dev_ok(logits, labels, alpha, coef, grad2)
+    N, Cc = int(logits.shape[0]), int(logits.shape[1])
+    S = logits.numel() // (N * Cc)
+    dz = torch.empty_like(logits)
+    check(_lib.lib().cbim_focal_bwd(_p(logits), _p(labels), _p(alpha), _p(coef), _p(grad2), _p(dz), float(gamma),
+                                    int(bool(with_dice)), N, Cc, S, _stream(logits)), "focal_bwd")
+    return dz
+
+
 def ncdhw_to_ndhwc(x: torch.Tensor, dtype: torch.dtype):
     _dev_ok(x)
     N, Cc = int(x.shape[0]), int(x.shape[1])

@@ -1,5 +1,5 @@
-"""Loss modules with the reference's call surface (/root/reference/training/losses.py:8-58,
-/root/reference/train.py:80-81,212), computed by the fused HIP Dice+CE kernels."""
+"""Loss modules with the reference's call surface (/root/reference/training/losses.py:8-98,
+/root/reference/train.py:80-81,212), computed by the fused HIP Dice+CE and focal kernels."""
 import torch
 import torch.nn as nn
 
@@ -34,6 +34,54 @@ class DiceCELoss(nn.Module):
     def forward(self, logits, label):
         with torch.autocast(device_type=logits.device.type, enabled=False):
             return Fn.DiceCEFn.apply(logits, label, self.weight)[2]
+
+
+def _focal_args(class_num, alpha, gamma):
+    gamma = float(gamma)
+    if not gamma >= 0.0 or gamma == float("inf"):
+        raise ValueError(f"gamma must be a finite number >= 0 (got {gamma})")
+    if alpha is not None:
+        alpha = torch.as_tensor(alpha, dtype=torch.float32).detach().clone().reshape(-1)
+        if class_num is None or int(alpha.numel()) != int(class_num):
+            raise ValueError(f"alpha has {int(alpha.numel())} entries for class_num = {class_num}")
+    return alpha, gamma
+
+
+class FocalLoss(nn.Module):
+    """FocalLoss(class_num, alpha, gamma, size_average)(preds[B,C,...], targets[B,...] int64) — losses.py:60-98: the mean (or the
+    sum) over all voxels of -alpha[y] (1 - p)^gamma log p.  The target has NO channel axis here (the reference's convention for
+    this module, unlike DiceLoss); a [B,1,...] target is viewed as [B,...]."""
+
+    def __init__(self, class_num, alpha=None, gamma=2, size_average=True):
+        super().__init__()
+        alpha, self.gamma = _focal_args(class_num, alpha, gamma)
+        self.class_num, self.size_average = int(class_num), size_average
+        self.register_buffer("alpha", alpha)
+
+    def forward(self, preds, targets):
+        if int(preds.shape[1]) != self.class_num:
+            raise ValueError(f"FocalLoss(class_num={self.class_num}) called with {int(preds.shape[1])} channels")
+        with torch.autocast(device_type=preds.device.type, enabled=False):
+            out = Fn.FocalFn.apply(preds, targets, self.alpha, self.gamma, False)
+            return out[1] if self.size_average else out[0]
+
+
+class DiceFocalLoss(nn.Module):
+    """FocalLoss(class_num, alpha, gamma)(logits, label.squeeze(1)) + DiceLoss()(logits, label) in one pass: the focal + Dice
+    recipe as a drop-in for DiceCELoss (label [B,1,...])."""
+
+    def __init__(self, class_num=None, alpha=None, gamma=2):
+        super().__init__()
+        alpha, self.gamma = _focal_args(class_num, alpha, gamma)
+        self.class_num = None if class_num is None else int(class_num)
+        self.register_buffer("alpha", alpha)
+
+    def forward(self, logits, label):
+        if self.class_num is not None and int(logits.shape[1]) != self.class_num:
+            raise ValueError(f"DiceFocalLoss(class_num={self.class_num}) called with {int(logits.shape[1])} channels")
+        with torch.autocast(device_type=logits.device.type, enabled=False):
+            out = Fn.FocalFn.apply(logits, label, self.alpha, self.gamma, True)
+            return out[4]
 
 
 def check_labels(reset: bool = True) -> int:

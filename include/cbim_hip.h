@@ -354,6 +354,27 @@ int cbim_dice_ce_bwd(const float* logits, const int64_t* labels, const float* we
                      const float* grad_out, float* dlogits, int N, int C, int64_t S, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Loss: FocalLoss(class_num, alpha, gamma)(logits, label) [+ DiceLoss()(logits, label)]
+ * (training/losses.py:60-98 [+ :8-58]) in one read of the logits; tensors as above, C <= 32.
+ * Per voxel L = -alpha[y] * q^gamma * log p with p = softmax(z)[y] and q = sum_{c != y} softmax(z)[c] (not 1 - p);
+ * alpha float [C] or NULL (all ones), gamma a finite float >= 0 (0 is plain -alpha[y] log p; q = 0 gives loss and gradient 0).
+ * fwd: out float[5]: out[0]=sum of L over the N*S voxels, out[1]=out[0]/(N*S), out[2]=Dice (0 unless with_dice),
+ *      out[3]=number of labels outside [0,C) (handled as in the CE + Dice entry points: excluded, counted; the mean still
+ *      divides by N*S), out[4]=out[1]+out[2] in float32.  with_dice != 0: the Dice term is that of the CE + Dice entry points bit for bit and coef float [3C + 1] is laid
+ *      out like theirs ([2][C] class coefficients, coef[2C] = 1/(N*S), [C] per-class terms); with_dice == 0: coef may be NULL.
+ *      workspace: cbim_focal_workspace(N,C,S).
+ * bwd: dlogits = grad_out[0] * d out[0]/dlogits + grad_out[1] * d out[2]/dlogits (grad_out: DEVICE float[2]; a mean's
+ *      1/(N*S) is folded into grad_out[0] by the caller; grad_out[1] is not read unless with_dice).
+ * ------------------------------------------------------------------------------------------ */
+size_t cbim_focal_workspace(int N, int C, int64_t S);
+int cbim_focal_fwd(const float* logits, const int64_t* labels, const float* alpha, float gamma, int with_dice,
+                   int N, int C, int64_t S, float* out, float* coef, void* workspace, size_t ws_bytes,
+                   void* stream);
+int cbim_focal_bwd(const float* logits, const int64_t* labels, const float* alpha, const float* coef,
+                   const float* grad_out, float* dlogits, float gamma, int with_dice, int N, int C, int64_t S,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device augmentation — training/augmentation.py (tensor_img [1,C,D,H,W] fp32, tensor_lab
  * [1,1,D,H,W] int8|int64), called per sample from the dataset (training/dataset/dim3/
  * dataset_amos_ct.py:121-153).  Random parameters are drawn by the HOST in the reference's order.
