@@ -32,13 +32,6 @@
 #include "conv_r32.h"
 #include <stdlib.h>
 
-// timing ablations of tools/conv_ablate.py (wrong results): compiled in only with `make EXTRA=-DCBIM_IGEMM_DBG_RT`
-#ifdef CBIM_IGEMM_DBG_RT
-#define I_DBG (p.dbg)
-#else
-#define I_DBG 0
-#endif
-
 namespace cbim {
 
 static constexpr int NT = 512;
@@ -64,7 +57,7 @@ struct IgemmParams {
   int hD, hH, hW;                  // halo extent = tile + k - 1
   int n_chunks, taps;
   unsigned mHW, mW;                // ceil(2^20 / (hH*hW)), ceil(2^20 / hW): division by multiply
-  int dbg;                         // timing ablations of rounds 1-3 (tools/archive); always 0
+  int pad_ = 0;                    // unused: without it the arguments below move and k_conv_igemm spills more SGPRs (profiles/switch_table_codegen.txt)
   int P;                           // records per image of `partials` (cbim_conv3d_num_tiles)
   int ksplit;                      // > 1: blockIdx.z owns a slice of the Cin chunks, raw fp32 partials go to ws
   float* ws;                       // [ksplit][N*Do*Ho*Wo][Cout] fp32
@@ -174,7 +167,6 @@ __global__ void __launch_bounds__(NTH, NTH == 256 ? 2 : 1) k_conv_igemm(IgemmPar
 
   // ---- weight stage s -> LDS buffer (s & 1) by LDS-DMA ------------------------------------------------
   auto dma_stage = [&](int q, int kd, int buf) {
-    if (I_DBG & 2) return;
     const unsigned char* src = (const unsigned char*)p.w +
         ((size_t)nb * p.n_chunks + q) * ((size_t)p.kD * stage_bytes) + (size_t)kd * stage_bytes;
     unsigned char* dst = smem + b_base + (unsigned)buf * stage_bytes;
@@ -243,7 +235,7 @@ __global__ void __launch_bounds__(NTH, NTH == 256 ? 2 : 1) k_conv_igemm(IgemmPar
       const unsigned hd = pk & 255u, hh = (pk >> 8) & 255u, hw = (pk >> 16) & 255u;
       // every thread issues exactly UH loads (discarded items read the safe row): the stage-end wait can then
       // leave exactly these UH loads in flight (wait_vm<UH>)
-      const bool ld = !(I_DBG & 1) && (pk >> 24) != 0 && c_ok && (unsigned)(id0 + (int)hd) < (unsigned)p.Di &&
+      const bool ld = (pk >> 24) != 0 && c_ok && (unsigned)(id0 + (int)hd) < (unsigned)p.Di &&
                       (unsigned)(ih0 + (int)hh) < (unsigned)p.Hi && (unsigned)(iw0 + (int)hw) < (unsigned)p.Wi;
       const unsigned rel = umad24(umad24(hd, (unsigned)p.Hi, hh), (unsigned)p.Wi, hw);
       const unsigned voff = ld ? umad24(rel, stride_b, c_byte) : safe;
@@ -534,7 +526,7 @@ __global__ void __launch_bounds__(NTH, NTH == 256 ? 2 : 1) k_conv_igemm(IgemmPar
                   for (int j = 0; j < CPC; ++j) { float d = v[j] - sh[j]; s0[j] += d; s1[j] += d * d; }
                 }
                 cnt += 1.f;
-                if (!(I_DBG & 4)) *(u32x4*)(y_tile + umad24(rel, y_sb, cb)) = Elem<T>::pack(v);
+                *(u32x4*)(y_tile + umad24(rel, y_sb, cb)) = Elem<T>::pack(v);
               }
             }
           }
@@ -1191,16 +1183,13 @@ extern "C" int cbim_conv3d_igemm(const cbim_conv_desc* d, const void* x, int64_t
   int KC = kc_of(d->dtype);
   p.n_chunks = (d->Cin + KC - 1) / KC;
   p.taps = d->kD * d->kH * d->kW;
-  p.dbg = 0;
   int BN = 32 * c.NTL;
   size_t smem = (size_t)p.hD * p.hH * p.hW * RB + 2 * (size_t)d->kH * d->kW * KG * 2 * BN * 16 +
                 (size_t)nw * BN * 3 * sizeof(float) + 64 * 2 * sizeof(float) +
                 ((size_t)d->kH * d->kW * KG * 2 * BN * 16 < (size_t)nw * 4096 ? (size_t)nw * 4096 : 0);
   CBIM_CHECK(smem <= 160 * 1024, CBIM_EUNSUPPORTED, "conv tile needs %zu B of LDS", smem);
-  int64_t n_tiles = (int64_t)d->N * p.tiles_d * p.tiles_h * p.tiles_w;
   int n_nblk = (d->Cout + BN - 1) / BN;
   const int64_t G = igemm_grid_x(d, c);
-  (void)n_tiles;
   p.P = cbim_conv3d_num_tiles(d);
   const int P_records = p.P;
   p.ksplit = pick_ksplit(d, c);
@@ -1238,15 +1227,13 @@ extern "C" int cbim_conv3d_igemm(const cbim_conv_desc* d, const void* x, int64_t
     // main kernel writes raw partials; the finish kernel owns residual / mask / statistics / store
     IgemmParams q = p;
     q.res = nullptr; q.mx = nullptr; q.partials = nullptr;
-    static const bool k3s_on = true;
-    const bool k3s = k3s_on && d->kH == 3 && d->kW == 3 && c.tH == 8;
+    const bool k3s = d->kH == 3 && d->kW == 3 && c.tH == 8;
     int rc = d->dtype == CBIM_BF16 ? dispatch_act<bf16_tag>(d->act, k3s, c, q, grid, smem, st)
                                    : dispatch_act<float>(d->act, k3s, c, q, grid, smem, st);
     if (rc) return rc;
     return launch_finish(d, workspace, p.ksplit, res, res_stride, mask_x, mask_stride, mask_stats, y, y_stride, partials, P_records, st);
   }
-  static const bool k3_on = true;
-  const bool k3 = k3_on && d->kH == 3 && d->kW == 3 && c.tH == 8;   // hW == hH == 10: compile-time tap offsets
+  const bool k3 = d->kH == 3 && d->kW == 3 && c.tH == 8;   // hW == hH == 10: compile-time tap offsets
   return d->dtype == CBIM_BF16 ? dispatch_act<bf16_tag>(d->act, k3, c, p, grid, smem, st)
                                : dispatch_act<float>(d->act, k3, c, p, grid, smem, st);
 }

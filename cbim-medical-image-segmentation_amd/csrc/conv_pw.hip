@@ -25,6 +25,7 @@
 //     tiles), fixed merge order.
 #include "cbim_common.h"
 #include "gfx950_prims.h"
+#include "cbim_switches.h"
 #include "conv_r32.h"
 #include <stdlib.h>
 
@@ -485,14 +486,6 @@ __global__ void __launch_bounds__(PW_NT, 2) k_pw_wgrad(PwgParams p) {
 
 using namespace cbim;
 
-static int g_pw_on = 1;
-/* process-wide switch (tests, A/B): 0 = pointwise convolutions stay on k_conv_igemm; returns the old value */
-extern "C" int cbim_conv_pw_enable(int on) {
-  const int old = g_pw_on;
-  if (on >= 0) g_pw_on = on ? 1 : 0;
-  return old;
-}
-
 static void pw_strips(int64_t S, int rows, int* tiles, int* tps, int* Pn) {
   const int64_t t = (S + rows - 1) / rows;
   int64_t per = (t + 511) / 512;
@@ -501,7 +494,7 @@ static void pw_strips(int64_t S, int rows, int* tiles, int* tps, int* Pn) {
 }
 
 static bool pw_desc_ok(const cbim_conv_desc* d) {
-  return g_pw_on && d->dtype == CBIM_BF16 && d->kD == 1 && d->kH == 1 && d->kW == 1 && d->pD == 0 && d->pH == 0 && d->pW == 0 &&
+  return sw(SW_CONV_PW) && d->dtype == CBIM_BF16 && d->kD == 1 && d->kH == 1 && d->kW == 1 && d->pD == 0 && d->pH == 0 && d->pW == 0 &&
          d->Cin % 8 == 0 && d->Cout % 8 == 0 && d->Cin <= 4096 && d->Di == d->Do && d->Hi == d->Ho && d->Wi == d->Wo &&
          (int64_t)d->Do * d->Ho * d->Wo * PW_ROWS < ((int64_t)1 << 40);
 }

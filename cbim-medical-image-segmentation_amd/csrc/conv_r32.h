@@ -18,7 +18,7 @@ struct R32Params {
   int N, Di, Hi, Wi, Do, Ho, Wo, Cout;
   int pD, pH, pW, act;
   int tiles_d, tiles_h, tiles_w;
-  int dbg; // timing ablations for tools/ (env CBIM_R32_DBG); 0 in production
+  int pad_ = 0;   // unused: without it the kernel arguments below move and k_conv3_r32 / k_conv3_rw spill more SGPRs (profiles/switch_table_codegen.txt)
   int P;   // records per image of `partials` (cbim_conv3d_num_tiles)
   // k_conv3_rw split-K (low-resolution layers): blockIdx.z owns a slice of the Cin chunks and writes raw fp32 partial sums
   // ws[ksplit][N*Do*Ho*Wo][Cout] for k_splitk_finish (conv_igemm.hip); 1 / nullptr otherwise

@@ -31,20 +31,13 @@
 // partial-record format as conv_igemm.hip.
 #include "cbim_common.h"
 #include "gfx950_prims.h"
+#include "cbim_switches.h"
 #include "conv_r32.h"
 #include <stdlib.h>
 
 namespace cbim {
 
 static constexpr int R_RB = 64;                 // bytes per halo row (32 bf16 channels)
-// timing ablations of tools/r32_ablate.py (wrong results): compiled in only with `make EXTRA=-DCBIM_R32_DBG_RT` — as a
-// run-time parameter every test is a scalar branch, and the 90 of them inside the MFMA loop (one per fragment read) cut
-// the loop into basic blocks the scheduler cannot interleave across
-#ifdef CBIM_R32_DBG_RT
-#define R_DBG (p.dbg)
-#else
-#define R_DBG 0
-#endif
 #ifndef R32_LS_SINGLE
 #define R32_LS_SINGLE 0   // measured: 218 vs 183 us on 32->32 @128^3 (the per-tile butterfly costs more than the 10 spilled registers)
 #endif
@@ -222,7 +215,7 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
     unsigned hd, hh, hw, off;
     bool exists;
     item_get(u, sb, hd, hh, hw, exists, off);
-    const bool ld = !(R_DBG & 1) && exists && (unsigned)(id0 + (int)hd) < (unsigned)p.Di &&
+    const bool ld = exists && (unsigned)(id0 + (int)hd) < (unsigned)p.Di &&
                     (unsigned)(ih0 + (int)hh) < (unsigned)p.Hi && (unsigned)(iw0 + (int)hw) < (unsigned)p.Wi;
     return (ld ? tbase : (const unsigned char*)g_r32_zero) + (ld ? off : 0u);
   };
@@ -437,7 +430,7 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
     //     plane i feeds the MFMAs (n-tile i, kd 0), (i-1, kd 1), (i-2, kd 2).  The halo of the next tile is fetched by
     //     LDS-DMA during the first steps; TR: a piece is transformed in place four steps after its fetch.
     //     Branch-free (the strip's last tile re-fetches itself into the idle buffer).
-    if (!(R_DBG & 2)) {
+    {
       constexpr int RING = 5, PLN = TD + 2, SEQ = 9 * HP * PLN;   // fragment reads of a tile, in order
       u32x4 xr[RING];
       auto frag_addr = [&](int e) -> unsigned {                   // e = ((kh*3 + kw) * HP + hp) * PLN + plane
@@ -472,7 +465,7 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
             const int e = (s * HP + hp) * PLN + i;
             // read RING-1 entries ahead; the fences keep the compiler from sinking the read next to its use (it then
             // waits a full LDS round trip every third MFMA: measured 57 % of the MFMA rate)
-            if (e + RING - 1 < SEQ && !(R_DBG & 128)) xr[(e + RING - 1) % RING] = *(const u32x4*)(smem + frag_addr(e + RING - 1));
+            if (e + RING - 1 < SEQ) xr[(e + RING - 1) % RING] = *(const u32x4*)(smem + frag_addr(e + RING - 1));
             CBIM_SCHED_FENCE();
 #pragma unroll
             for (int kd = 0; kd < 3; ++kd) {
@@ -524,7 +517,7 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
     if (last_cc) {      // (a branch, not a predicate: the units in between must not touch — reload — any of this)
 #pragma unroll
       for (int pr = 0; pr < NPAIR; ++pr) {
-        const bool in = pair_in(pr) && c_ok && !(R_DBG & (4 | 8));
+        const bool in = pair_in(pr) && c_ok;
         const unsigned rel = pair_rel(pr);
         if (in) {
           if (MX) rq[pr] = *(const u32x4*)(mx_tile + (umul24(rel, mx_sb) + cb));
@@ -542,7 +535,7 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
     __syncthreads();
     // (C) epilogue of this tile — no barrier inside (except at an image change); its stores drain under the next
     //     tile's MFMAs
-    if (last_cc && !(R_DBG & 4)) {
+    if (last_cc) {
       if (want_part && n != run_n) { flush_stats(run_n); run_n = n; }
       // statistics of this tile: running per-lane sums (single chunk) or tile-local sums reduced below (MC)
       float l0[8], l1[8], lsh[MX ? 1 : 8];
@@ -615,7 +608,7 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
             v[2 * j] += __uint_as_float(rw[j] << 16);
             v[2 * j + 1] += __uint_as_float(rw[j] & 0xffff0000u);
           }
-          if (want_part && !(R_DBG & 32)) {
+          if (want_part) {
             if (!SHSET) {            // common shift of the 32 lanes that hold this chunk: any finite value near
               SHSET = true;             // the data works (shifted moments); taken from the group's first lane
 #pragma unroll
@@ -632,76 +625,50 @@ __global__ void __launch_bounds__(RGeom<TD>::NT, TD == 8 ? 1 : 2) k_conv3_r32(R3
             }
           }
         }
-        if (in && c_ok && !(R_DBG & 16)) *(u32x4*)(y_tile + (umul24(rel, y_sb) + cb)) = Elem<bf16_tag>::pack(v);
+        if (in && c_ok) *(u32x4*)(y_tile + (umul24(rel, y_sb) + cb)) = Elem<bf16_tag>::pack(v);
         CNT += live;
       }
-      if (LS && want_part && !(R_DBG & 32)) tile_stats(l0, l1, lsh, lcnt);
+      if (LS && want_part) tile_stats(l0, l1, lsh, lcnt);
     }
     cur = nxt;
     advance(nxt);
   }
-  if (want_part && !(R_DBG & 64)) flush_stats(run_n);
+  if (want_part) flush_stats(run_n);
 }
 
 }  // namespace cbim
 
 using namespace cbim;
 
-static int64_t g_r32_min_voxels = 262144;   // same threshold as the 8x8x8 tile configuration of k_conv_igemm
-static int r32_tile_depth();
-
-// mode (frozen at 2 since round 3): 0 off, 1 the single-chunk layers only (Cin = 32, Cout <= 32), 2 (default) every multiple of 32
-static int r32_mode() {
-  static const int m = 2;
-  return m;
-}
 bool cbim_conv_r32_eligible(const cbim_conv_desc* d, const void* x2, int cin_split, const float* in_stats, const void* res,
                             const void* mask_x) {
-  const int mode = r32_mode();
-  if (!mode || d->dtype != CBIM_BF16) return false;
+  if (d->dtype != CBIM_BF16) return false;
   if (d->kD != 3 || d->kH != 3 || d->kW != 3 || d->Cin % 32 != 0 || !(d->Cout <= 32 || d->Cout % 32 == 0)) return false;
-  if (mode == 1 && (d->Cin != 32 || d->Cout > 32 || x2)) return false;
-  if (d->Cin > 32 * RGeom<8>::MAXC || (d->Cin > 32 && r32_tile_depth() != 8)) return false;
+  if (d->Cin > 32 * RGeom<8>::MAXC || (d->Cin > 32 && sw(SW_CONV_R32_TILE_DEPTH) != 8)) return false;
   if (x2 && (cin_split <= 0 || cin_split >= d->Cin || cin_split % 32 != 0)) return false;
   if (d->Do < 8 || d->Ho < 8 || d->Wo < 8) return false;
   if (!(d->act == CBIM_ACT_RELU || d->act == CBIM_ACT_NONE)) return false;
   if (mask_x && (in_stats || res)) return false;   // masked epilogue: raw input, no accumulate tensor
-  const int64_t S = (int64_t)d->Do * d->Ho * d->Wo;
-  if (g_r32_min_voxels == 0) return true;            // forced (tests, tools)
-  if (d->Cin == 32 && d->Cout <= 32) return S >= g_r32_min_voxels;   // at least ~2 tiles per CU
+  const int64_t S = (int64_t)d->Do * d->Ho * d->Wo, min_voxels = sw(SW_CONV_R32_MIN_VOXELS);
+  if (min_voxels == 0) return true;                  // forced (tests, tools)
+  if (d->Cin == 32 && d->Cout <= 32) return S >= min_voxels;   // at least ~2 tiles per CU
   // several chunks, measured against k_conv_igemm (profiles/r02_p_conv_bench_ab.txt).  Raw input (dgrad, LDS-DMA only):
   // ahead on every shape, 2-24 %.  Transformed input (forward: InstanceNorm + activation applied in LDS once per unit
   // and per Cout chunk): ahead for single-chunk inputs, where the 64-wide n-blocks of k_conv_igemm are half empty
   // (Cout = 32, 96, ...) and at 32^3 where its tiles are too few; 10-15 % behind on 64-multiples at >= 64^3.
   const int64_t tiles = (int64_t)d->N * ((d->Do + 7) / 8) * ((d->Ho + 7) / 8) * ((d->Wo + 7) / 8);
   const int n_oc = (d->Cout + 31) / 32;
-  if (S >= g_r32_min_voxels) return !in_stats || d->Cin == 32 || d->Cout % 64 != 0;
+  if (S >= min_voxels) return !in_stats || d->Cin == 32 || d->Cout % 64 != 0;
   // low-resolution layers: enough (tile strip, Cout chunk) workgroups to fill half the chip.  Raw inputs (round 3,
   // profiles/r03_t_small_layers_r32.txt): 576->512 @16^3 138 -> 97 us forward, 124 -> 86 us dgrad; 128->512 @16^3 forward
   // 46 -> 35 us; 256->64 @32^3 dgrad 68 -> 50 us; below 128 workgroups (256->256 @16^3, everything at 8^3) the split-K
   // k_conv_igemm stays ahead
   if (!in_stats) return tiles * n_oc >= 128;
-  return S >= g_r32_min_voxels / 8 && tiles * n_oc >= 192;
-}
-
-extern "C" int64_t cbim_conv_r32_min_voxels(int64_t v) {
-  const int64_t old = g_r32_min_voxels;
-  if (v >= 0) g_r32_min_voxels = v;
-  return old;
-}
-
-// 8: one 512-thread workgroup per CU on 8x8x8 tiles (default); 4: two 256-thread workgroups per CU on 4x8x8 tiles —
-// measured 5-15 % slower on 32->32 @128^3 (more halo per voxel, and the MFMA phase, not the overlap, is what limits)
-static int g_r32_td = 8;
-static int r32_tile_depth() { return g_r32_td; }
-extern "C" int cbim_conv_r32_tile_depth(int td) {
-  const int old = g_r32_td;
-  if (td == 4 || td == 8) g_r32_td = td;
-  return old;
+  return S >= min_voxels / 8 && tiles * n_oc >= 192;
 }
 
 int64_t cbim_conv_r32_grid(const cbim_conv_desc* d) {
-  const int td = r32_tile_depth();
+  const int td = (int)sw(SW_CONV_R32_TILE_DEPTH);
   const int64_t n_tiles = (int64_t)d->N * ((d->Do + td - 1) / td) * ((d->Ho + 7) / 8) * ((d->Wo + 7) / 8);
   const int n_oc = (d->Cout + 31) / 32;
   int64_t cap = (td == 8 ? 256 : 512) / n_oc;      // about one workgroup per CU over all Cout chunks
@@ -731,7 +698,7 @@ static int r32_launch_mc(const R32Params& p, dim3 grid, hipStream_t st) {
 template <int ACT, bool TR, bool MX>
 static int r32_launch(const R32Params& p, dim3 grid, hipStream_t st) {
   if (p.NC > 1) return r32_launch_mc<ACT, TR, MX, 8, true>(p, grid, st);     // (eligibility: tile depth 8 only)
-  return r32_tile_depth() == 8 ? r32_launch_mc<ACT, TR, MX, 8, false>(p, grid, st) : r32_launch_mc<ACT, TR, MX, 4, false>(p, grid, st);
+  return sw(SW_CONV_R32_TILE_DEPTH) == 8 ? r32_launch_mc<ACT, TR, MX, 8, false>(p, grid, st) : r32_launch_mc<ACT, TR, MX, 4, false>(p, grid, st);
 }
 
 int cbim_conv_r32_launch(const cbim_conv_desc* d, const void* x, int64_t x_stride, const void* x2, int64_t x2_stride,
@@ -747,9 +714,8 @@ int cbim_conv_r32_launch(const cbim_conv_desc* d, const void* x, int64_t x_strid
   p.y = y; p.y_stride = y_stride; p.partials = partials;
   p.N = d->N; p.Di = d->Di; p.Hi = d->Hi; p.Wi = d->Wi; p.Do = d->Do; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
   p.pD = d->pD; p.pH = d->pH; p.pW = d->pW; p.act = d->act;
-  const int td = r32_tile_depth();
+  const int td = (int)sw(SW_CONV_R32_TILE_DEPTH);
   p.tiles_d = (d->Do + td - 1) / td; p.tiles_h = (d->Ho + 7) / 8; p.tiles_w = (d->Wo + 7) / 8;
-  p.dbg = 0;   // tools/r32_ablate.py timing ablations; 0 in production
   p.P = cbim_conv3d_num_tiles(d);
   CBIM_CHECK(!partials || p.P >= (int)cbim_conv_r32_grid(d), CBIM_EINVAL, "conv r32: %d partial records < grid", p.P);
   {

@@ -28,8 +28,8 @@
 // nn.Conv3d in ConvNormAct (/root/reference/model/dim3/conv_layers.py:29-38, 48-49: zero padding after the activation).
 #include "cbim_common.h"
 #include "gfx950_prims.h"
+#include "cbim_switches.h"
 #include "conv_r32.h"
-#include <stdlib.h>
 #include <stdio.h>
 
 namespace cbim {
@@ -542,18 +542,6 @@ __global__ void __launch_bounds__(512, 1) k_conv3_rw48(R32Params p) {
 
 using namespace cbim;
 
-// g_rw_on (cbim_conv_rw_enable): 0 off (every call stays on k_conv3_r32 / k_conv_igemm), 1 (default) on
-static int g_rw_on = 1;
-// g_rw_wide (cbim_conv_rw_enable): 0 never, 1 (default) the wide form wherever Cout is a multiple of 64 and the grid still fills the chip,
-// 2 wherever Cout is a multiple of 64
-static int g_rw_wide = 1;
-extern "C" int cbim_conv_rw_enable(int on, int wide) {
-  const int old = g_rw_on | (g_rw_wide << 1);
-  if (on >= 0) g_rw_on = on & 1;
-  if (wide >= 0) g_rw_wide = wide;
-  return old;
-}
-
 static int64_t rw_tiles(const cbim_conv_desc* d) {
   return (int64_t)d->N * ((d->Do + 7) / 8) * ((d->Ho + 7) / 8) * ((d->Wo + 7) / 8);
 }
@@ -562,8 +550,9 @@ static int64_t rw_tiles(const cbim_conv_desc* d) {
 // is slower per output than the narrow one and has to be amortised: 96->64 @128^3 687 -> 609 us, 192->128 @64^3 269 -> 251,
 // 384->256 @32^3 136 -> 127, but 64->64 @64^3 59 -> 63 (profiles/r04_g_conv_rw_ab.txt)
 static bool rw_wide(const cbim_conv_desc* d) {
-  if (!g_rw_wide || d->Cout % 64 != 0) return false;
-  if (g_rw_wide == 2) return true;                                  // (forced: tests)
+  const int64_t wide = sw(SW_CONV_RW_WIDE);
+  if (!wide || d->Cout % 64 != 0) return false;
+  if (wide == 2) return true;                                       // (forced: tests)
   return d->Cin >= 96 && rw_tiles(d) * (d->Cout / 64) >= 192;
 }
 
@@ -572,7 +561,7 @@ static bool rw_wide(const cbim_conv_desc* d) {
 bool cbim_conv_rw_eligible(const cbim_conv_desc* d, const void* x, int64_t x_stride, const void* x2, int64_t x2_stride,
                            const float* in_stats, const void* mask_x, const float* mask_stats) {
   (void)x; (void)x2;
-  if (!g_rw_on || in_stats) return false;
+  if (!sw(SW_CONV_RW) || in_stats) return false;
   if (mask_x && (mask_stats || d->act != CBIM_ACT_RELU)) return false;
   if (d->pD > 1 || d->pH > 1 || d->pW > 1 || d->pD < 0 || d->pH < 0 || d->pW < 0) return false;
   // scalar + vector offset of the buffer loads stay below 2^31 inside one image (num_records = 2^31)
@@ -585,17 +574,12 @@ bool cbim_conv_rw_eligible(const cbim_conv_desc* d, const void* x, int64_t x_str
 // Round 6: 48 output channels per workgroup (k_conv3_rw48) — Cout in multiples of 48 where the 32-channel kernels do not apply
 // (Cin or Cout not a multiple of 32: SwinUNETR's 48 -> 48, 96 -> 48 and the 48 -> 96 input gradient), Cin any multiple of 8
 // (the last 32-channel chunk is zero-filled past Cin).  CBIM_CONV_RW48=0 keeps those layers on k_conv_igemm (A/B runs).
-static int g_rw48 = getenv("CBIM_CONV_RW48") ? atoi(getenv("CBIM_CONV_RW48")) : 1;
-extern "C" int cbim_conv_rw48_enable(int on) {
-  const int old = g_rw48;
-  if (on >= 0) g_rw48 = on;
-  return old;
-}
 static bool rw48_shape(const cbim_conv_desc* d) {
-  if (!g_rw_on || !g_rw48 || d->dtype != CBIM_BF16 || d->kD != 3 || d->kH != 3 || d->kW != 3) return false;
+  const int64_t rw48 = sw(SW_CONV_RW48);
+  if (!sw(SW_CONV_RW) || !rw48 || d->dtype != CBIM_BF16 || d->kD != 3 || d->kH != 3 || d->kW != 3) return false;
   if (d->Cout % 48 != 0 || d->Cin % 8 != 0 || (d->Cin % 32 == 0 && d->Cout % 32 == 0)) return false;
   if (d->Do < 8 || d->Ho < 8 || d->Wo < 8) return false;
-  if (g_rw48 == 2) return true;                                     // (forced: tests)
+  if (rw48 == 2) return true;                                       // (forced: tests)
   return rw_tiles(d) * (d->Cout / 48) >= 128;
 }
 bool cbim_conv_rw48_eligible(const cbim_conv_desc* d, const void* x, int64_t x_stride, const void* x2, int64_t x2_stride, int cin_split,
@@ -603,10 +587,7 @@ bool cbim_conv_rw48_eligible(const cbim_conv_desc* d, const void* x, int64_t x_s
   if (!rw48_shape(d) || in_stats) return false;
   if (mask_x && (mask_stats || !(d->act == CBIM_ACT_RELU || d->act == CBIM_ACT_LRELU))) return false;
   if (x2 && (cin_split <= 0 || cin_split >= d->Cin || cin_split % 32 != 0)) return false;
-  const int keep = g_rw_on;                                          // (the addressing limits of k_conv3_rw)
-  const bool ok = cbim_conv_rw_eligible(d, x, x_stride, x2, x2_stride, nullptr, nullptr, nullptr);
-  (void)keep;
-  return ok;
+  return cbim_conv_rw_eligible(d, x, x_stride, x2, x2_stride, nullptr, nullptr, nullptr);   // (the addressing limits of k_conv3_rw)
 }
 // the same question without the call's tensors (Python picks the materialised-activation path of a block by it)
 extern "C" int cbim_conv_rw48_takes(const cbim_conv_desc* d) {
@@ -707,7 +688,6 @@ int cbim_conv_rw_launch(const cbim_conv_desc* d, const void* x, int64_t x_stride
   p.N = d->N; p.Di = d->Di; p.Hi = d->Hi; p.Wi = d->Wi; p.Do = d->Do; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
   p.pD = d->pD; p.pH = d->pH; p.pW = d->pW; p.act = d->act;
   p.tiles_d = (d->Do + 7) / 8; p.tiles_h = (d->Ho + 7) / 8; p.tiles_w = (d->Wo + 7) / 8;
-  p.dbg = 0;
   p.ksplit = 1; p.ws = nullptr;
   p.P = cbim_conv3d_num_tiles(d);
   const bool c48 = rw48_shape(d);
@@ -740,9 +720,8 @@ int cbim_conv_rw_launch(const cbim_conv_desc* d, const void* x, int64_t x_stride
 // split-K factor of a low-resolution layer: 0 when the layer already has >= 128 (tile, 32-cout block) workgroups or a single
 // Cin chunk; otherwise the divisor-free share-out of the Cin chunks that brings the launch closest to one workgroup per CU
 // (k_splitk_finish keeps one 16-byte output chunk per thread of 256: Cout <= 2048)
-static int g_rw_split = 1;
 int cbim_conv_rw_ksplit(const cbim_conv_desc* d) {
-  if (!g_rw_on || !g_rw_split || d->dtype != CBIM_BF16) return 0;
+  if (!sw(SW_CONV_RW) || d->dtype != CBIM_BF16) return 0;
   const int NC = d->Cin / 32;
   const int64_t wgs = rw_tiles(d) * ((d->Cout + 31) / 32);
   if (NC < 2 || wgs >= 128 || d->Cout / 8 > 256) return 0;
@@ -765,7 +744,7 @@ int cbim_conv_rw_split_launch(const cbim_conv_desc* d, const void* x, int64_t x_
   p.N = d->N; p.Di = d->Di; p.Hi = d->Hi; p.Wi = d->Wi; p.Do = d->Do; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
   p.pD = d->pD; p.pH = d->pH; p.pW = d->pW; p.act = d->act;
   p.tiles_d = (d->Do + 7) / 8; p.tiles_h = (d->Ho + 7) / 8; p.tiles_w = (d->Wo + 7) / 8;
-  p.dbg = 0; p.P = 0;
+  p.P = 0;
   p.ksplit = cbim_conv_rw_ksplit(d); p.ws = ws;
   CBIM_CHECK(p.ksplit > 1 && ws, CBIM_EINVAL, "conv rw split-K: not a split-K layer");
   CBIM_CHECK((int64_t)8 * d->Ho * d->Wo < (1 << 24), CBIM_EUNSUPPORTED, "conv rw split-K: output plane too large");

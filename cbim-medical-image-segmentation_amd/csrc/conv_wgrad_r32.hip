@@ -27,8 +27,8 @@
 // (/root/reference/model/dim3/conv_layers.py:29-38).
 #include "cbim_common.h"
 #include "gfx950_prims.h"
+#include "cbim_switches.h"
 #include "conv_wgrad_r32.h"
-#include <stdlib.h>
 #include <stdio.h>
 
 namespace cbim {
@@ -54,15 +54,11 @@ struct WR32Params {
   int tiles_d, tiles_h, tiles_w;
   int ci_blocks, Cout_pad, Cin_pad;   // 32-channel blocks of Cin; the gradient's own Cout, Cin (slab layout [Cout][Cin][27])
   int cin_bytes, cout_bytes;          // 2 Cin, 2 Cout: the 16-byte slots of a last block past them are zero-filled (round 6: 48 channels)
-  int dbg;   // timing ablations of round 3 (tools/archive); always 0
+  int pad_ = 0;   // unused: keeps `diag` at the kernel-argument offset k_wgrad_r32's scalar registers were allocated around (profiles/switch_table_codegen.txt)
   int diag;  // depthwise form: blockIdx.y = 32-channel group, only the diagonal (co == ci) of the 32 x 32 block is kept
 };
 
-// timing ablations of tools/wr32_ablate.py (wrong results): a COMPILE-TIME parameter of the kernel (as run-time tests they
-// were ~300 scalar branches per tile that cut the MFMA loop into basic blocks: +12 % kernel time, measured); the ablated
-// instantiations exist only in builds with `make EXTRA=-DCBIM_WR32_ABLATE`
-#define WR_DBG DBG
-// tuning knobs (tools/run_wr32_variants.sh builds and times the alternatives)
+// tuning knobs (`make EXTRA=-DWR32_RING=4 ...` builds an alternative)
 #ifndef WR32_RING
 #define WR32_RING 5          // input-fragment reads in flight ahead of their MFMAs (+1)
 #endif
@@ -82,7 +78,7 @@ __device__ unsigned long long g_wr32_prof[8][8];
 #define WR_STAMP(i) ((void)0)
 #endif
 
-template <int WV, int DBG = 0>
+template <int WV>
 __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
   constexpr int WR_NT = WV * 64;
   constexpr int NCH = WV == 8 ? 1 : 2;                                // co halves per wave
@@ -265,7 +261,7 @@ __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
     const Src rn = src_of(more ? nxt : cur);                           // (wave-uniform scalars + two selects: cheap)
     // (B) 9 (kh, kw) steps: the 10 halo-plane fragments stream through a ring of 5 registers; plane p feeds the taps
     //     (kd 0, dy plane p), (kd 1, p-1), (kd 2, p-2).  The next tile's halo is fetched during the first four steps.
-    if (!(WR_DBG & 2)) {
+    {
       constexpr int RING = WR32_RING, PLN = 10, SEQ = 9 * PLN;
       u32x4 xr[RING];
       auto frag = [&](int e) -> u32x4 {                                // e = (kh*3 + kw) * PLN + plane
@@ -282,7 +278,7 @@ __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
         const int kh = s / 3, kw = s % 3;
         // the next tile's pieces: halo planes 2 s, 2 s + 1 in steps 0..4, the dy pieces (the dy region is free: every wave
         // passed the barrier above with its fragments in registers) one per step in steps 1..4
-        if (more && !(WR_DBG & 1)) {
+        if (more) {
           if (s < 5) {
 #pragma unroll
             for (int q = 0; q < HS; ++q)
@@ -297,7 +293,7 @@ __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
 #pragma unroll
         for (int pl = 0; pl < PLN; ++pl) {
           const int e = s * PLN + pl;
-          if (e + RING - 1 < SEQ && !(WR_DBG & 4)) xr[(e + RING - 1) % RING] = frag(e + RING - 1);
+          if (e + RING - 1 < SEQ) xr[(e + RING - 1) % RING] = frag(e + RING - 1);
           CBIM_SCHED_FENCE();
 #if WR32_SETPRIO && !defined(CBIM_EMU)
           __builtin_amdgcn_s_setprio(3);
@@ -305,10 +301,7 @@ __global__ void __launch_bounds__(WV * 64, 1) k_wgrad_r32(WR32Params p) {
 #pragma unroll
           for (int kd = 0; kd < 3; ++kd) {
             const int i = pl - kd;
-#ifndef CBIM_EMU
-            if (WR_DBG & 8) asm volatile("" ::"v"(xr[e % RING]));   // (ablation: the fragment reads stay alive without the MFMAs)
-#endif
-            if (i >= 0 && i < 8 && !(WR_DBG & 8)) {
+            if (i >= 0 && i < 8) {
               const int tap = (kd * 3 + kh) * 3 + kw;
 #pragma unroll
               for (int c = 0; c < NCH; ++c)
@@ -425,35 +418,15 @@ __global__ void __launch_bounds__(512) k_wgrad_r32_reduce(const float* __restric
 
 using namespace cbim;
 
-// cbim_wgrad_r32_enable(0) keeps every weight gradient on k_conv_wgrad (tests: two-sided checks)
-static int g_wr32_on = 1;
-static int wr32_on() { return g_wr32_on; }
-// CBIM_WGRAD_R32_C16=0 keeps the layers whose channel counts are not multiples of 32 on k_conv_wgrad (A/B runs)
-static int g_wr32_c16 = getenv("CBIM_WGRAD_R32_C16") ? atoi(getenv("CBIM_WGRAD_R32_C16")) : 1;
-extern "C" int cbim_wgrad_r32_enable(int on) {
-  const int old = g_wr32_on;
-  if (on >= 0) g_wr32_on = on;
-  return old;
-}
-
-// cbim_wgrad_r32_waves(4 | 8): waves per workgroup (see k_wgrad_r32); process-wide knob for tests
-static int g_wr32_waves = 8;
-static int wr32_waves() { return g_wr32_waves; }
-extern "C" int cbim_wgrad_r32_waves(int w) {
-  const int old = g_wr32_waves;
-  if (w == 4 || w == 8) g_wr32_waves = w;
-  return old;
-}
-
 bool cbim_wgrad_r32_eligible(const cbim_conv_desc* d, const float* in_stats, const void* x2, int cin_split, const void* dy2,
                              int cout_split) {
-  if (!wr32_on() || d->dtype != CBIM_BF16 || in_stats) return false;
+  if (!sw(SW_WGRAD_R32) || d->dtype != CBIM_BF16 || in_stats) return false;
   if (d->kD != 3 || d->kH != 3 || d->kW != 3 || d->pD != 1 || d->pH != 1 || d->pW != 1) return false;
   // round 6: channel counts in multiples of 16 run with a zero-filled last 32-channel block (SwinUNETR's 48 / 96-channel layers:
   // 48 x 48 = four (32 x 32) pairs, nine sixteenths of them inside the gradient) — still ahead of k_conv_wgrad, which pads the same way
   if (d->Cin % 32 != 0 || d->Cout % 32 != 0) {
     // (Cin in multiples of 8 down to 8: the 8-channel padded network input of SwinUNETR's encoder1 — one quarter-filled block)
-    if (!g_wr32_c16 || d->Cin % 8 != 0 || d->Cout % 16 != 0 || d->Cout < 32) return false;
+    if (!sw(SW_WGRAD_R32_C16) || d->Cin % 8 != 0 || d->Cout % 16 != 0 || d->Cout < 32) return false;
   }
   if (x2 && (cin_split <= 0 || cin_split >= d->Cin || cin_split % 32 != 0)) return false;
   if (dy2 && (cout_split <= 0 || cout_split >= d->Cout || cout_split % 32 != 0)) return false;
@@ -480,7 +453,6 @@ int cbim_wgrad_r32_dw_strips(const cbim_conv_desc* d) {
   wr32_tiles(d, td, th, tw);
   return wr32_strips_for((int64_t)d->N * td * th * tw, (int64_t)(d->Cout / 32), (int64_t)27 * d->Cout * 4);
 }
-static int g_wr32_small_strips = 1;
 static int wr32_strips_for(int64_t n_tiles, int64_t pairs, int64_t slab) {
   int64_t gmax = (96ll << 20) / slab;
   if (gmax < 1) gmax = 1;
@@ -494,7 +466,7 @@ static int wr32_strips_for(int64_t n_tiles, int64_t pairs, int64_t slab) {
     // (small layers — at most 64 tiles, everything L2 / MALL resident — may break that rule when it saves a round of
     //  workgroups: 256 -> 256 @16^3 = 8 tiles x 64 pairs ran as 512 one-tile workgroups in two rounds)
     const bool off8 = pairs > 1 && gmax >= 8 && g % 8 != 0;
-    if (off8 && (n_tiles > 64 || !g_wr32_small_strips)) continue;
+    if (off8 && n_tiles > 64) continue;
     const double rounds = (double)((pairs * g + 255) / 256);
     const double cost = rounds * ((double)((n_tiles + g - 1) / g) + 1.5) + (off8 ? 0.25 : 0.0);
     if (cost < best_cost - 1e-9) { best_cost = cost; best = (int)g; }
@@ -536,7 +508,6 @@ static int wr32_launch(const cbim_conv_desc* d, const void* x, int64_t x_stride,
   wr32_tiles(d, p.tiles_d, p.tiles_h, p.tiles_w);
   p.ci_blocks = (d->Cin + 31) / 32; p.Cout_pad = d->Cout; p.Cin_pad = d->Cin;
   p.cin_bytes = d->Cin * 2; p.cout_bytes = d->Cout * 2;
-  p.dbg = 0;
   {
     // 32-bit byte offsets inside one halo box / one dy tile, built from 24-bit multiplies
     const int64_t box_rows = (int64_t)10 * d->Hi * d->Wi, xs = (x2 && x2_stride > x_stride ? x2_stride : x_stride) * 2;
@@ -558,17 +529,7 @@ static int wr32_launch(const cbim_conv_desc* d, const void* x, int64_t x_stride,
   }
 #endif
   dim3 grid((unsigned)strips, (unsigned)(diag ? d->Cout / 32 : ((d->Cout + 31) / 32) * ((d->Cin + 31) / 32)));
-#ifdef CBIM_WR32_ABLATE
-#define WR_ABL(W, D)                                                                                                   \
-  if (wr32_waves() == W && p.dbg == D) {                                                                               \
-    (void)hipFuncSetAttribute((const void*)k_wgrad_r32<W, D>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    CBIM_LAUNCH((k_wgrad_r32<W, D>), grid, dim3(W * 64), (size_t)WR_SMEM, (hipStream_t)stream, p);                     \
-  } else
-  WR_ABL(8, 1) WR_ABL(8, 2) WR_ABL(8, 4) WR_ABL(8, 8) WR_ABL(8, 5) WR_ABL(8, 9) WR_ABL(8, 12) WR_ABL(8, 13) WR_ABL(8, 3)
-  WR_ABL(4, 1) WR_ABL(4, 2) WR_ABL(4, 4) WR_ABL(4, 8) WR_ABL(4, 5) WR_ABL(4, 9) WR_ABL(4, 12) WR_ABL(4, 13) WR_ABL(4, 3)
-#undef WR_ABL
-#endif
-  if (wr32_waves() == 4) CBIM_LAUNCH(k_wgrad_r32<4>, grid, dim3(256), (size_t)WR_SMEM, (hipStream_t)stream, p);
+  if (sw(SW_WGRAD_R32_WAVES) == 4) CBIM_LAUNCH(k_wgrad_r32<4>, grid, dim3(256), (size_t)WR_SMEM, (hipStream_t)stream, p);
   else CBIM_LAUNCH(k_wgrad_r32<8>, grid, dim3(512), (size_t)WR_SMEM, (hipStream_t)stream, p);
 #ifdef CBIM_WR32_PROF
   {

@@ -17,6 +17,7 @@
 // channel c = d*heads + h (medformer_utils.py:43-51).  Map-side tensors are float32 [N][M][inner].
 #include "cbim_common.h"
 #include "gfx950_prims.h"
+#include "cbim_switches.h"
 #include "conv_wgrad_r32.h"
 #include <stdlib.h>
 
@@ -1359,15 +1360,6 @@ static int check_k(int kD, int kH, int kW) {
   return 0;
 }
 
-static int g_dw_lds = 1;
-/* process-wide switch (tests, A/B): 0 = the streaming depthwise kernel also where the LDS-tiled one applies; < 0 only queries;
- * returns the old value */
-extern "C" int cbim_dwconv_lds_enable(int on) {
-  const int old = g_dw_lds;
-  if (on >= 0) g_dw_lds = on ? 1 : 0;
-  return old;
-}
-
 extern "C" int cbim_dwconv3d(int dtype, const void* x, int64_t x_stride, const float* in_stats, int act,
                              const float* bias, const float* w, int flip, void* y, int64_t y_stride, int N, int D,
                              int H, int W, int C, int kD, int kH, int kW, void* stream) {
@@ -1385,7 +1377,7 @@ extern "C" int cbim_dwconv3d(int dtype, const void* x, int64_t x_stride, const f
     if (bx < 1) bx = 1;
     const int mode = !in_stats ? 0 : act == CBIM_ACT_RELU ? 1 : act == CBIM_ACT_NONE ? 2 : 3;
     static const int lds_on = 1;
-    if (lds_on && g_dw_lds) {      // LDS-tiled form (round 4): one sweep of loads, the input transformed once
+    if (lds_on && sw(SW_DWCONV_LDS)) {      // LDS-tiled form (round 4): one sweep of loads, the input transformed once
       const int tiles_d = (D + LTD - 1) / LTD, tiles_h = (H + LTH - 1) / LTH, tiles_w = (W + LTW - 1) / LTW;
       const int64_t tiles = (int64_t)N * tiles_d * tiles_h * tiles_w;
       const int lgroups = (cch + LG - 1) / LG;

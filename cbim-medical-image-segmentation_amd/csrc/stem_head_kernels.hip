@@ -7,6 +7,7 @@
 //         logits out (the layout nn.CrossEntropyLoss / DiceLoss consume, train.py:212).
 #include "cbim_common.h"
 #include "gfx950_prims.h"
+#include "cbim_switches.h"
 #include <stdlib.h>
 
 namespace cbim {
@@ -1020,14 +1021,6 @@ static StemCfg stem_cfg(int N, int Do, int Ho, int Wo) {
 
 using namespace cbim;
 
-static int g_stem_mfma = 1;
-/* process-wide switch (tests, A/B): 0 = the VALU stem kernels also where the matrix-core ones apply; returns the old value */
-extern "C" int cbim_stem_mfma_enable(int on) {
-  const int old = g_stem_mfma;
-  g_stem_mfma = on ? 1 : 0;
-  return old;
-}
-
 static int stem_check(int dtype, int Cin, int Cout, int kD, int kH, int kW) {
   CBIM_CHECK(dtype == CBIM_F32 || dtype == CBIM_BF16, CBIM_EINVAL, "bad dtype");
   int cpc = dtype == CBIM_BF16 ? 8 : 4;
@@ -1058,7 +1051,7 @@ extern "C" int cbim_stem_conv_fwd(int dtype_out, const float* x, const float* w,
   CBIM_CHECK(smem <= 64 * 1024, CBIM_EUNSUPPORTED, "stem needs %zu B of LDS", smem);
   dim3 grid((unsigned)(N * p.tiles_d * p.tiles_h * p.tiles_w));
   hipStream_t st = (hipStream_t)stream;
-  if (g_stem_mfma && dtype_out == CBIM_BF16 && Cin == 1 && Cout % 32 == 0 && Cout <= 128 && p.taps <= MAXTAPS &&
+  if (sw(SW_STEM_MFMA) && dtype_out == CBIM_BF16 && Cin == 1 && Cout % 32 == 0 && Cout <= 128 && p.taps <= MAXTAPS &&
       kD <= 3 && kH <= 3 && kW <= 3) {   // matrix-core form
     const size_t sm = (size_t)3 * NT * sizeof(unsigned);
     dim3 pg(grid.x < 2048u ? grid.x : 2048u);             // persistent workgroups: the weight fragments are built once
@@ -1103,7 +1096,7 @@ extern "C" int cbim_stem_conv_wgrad(int dtype, const float* x, const void* dy, f
                 N * p.strips_per_n, Cin, p.taps, Cout);
     return CBIM_LAST_LAUNCH() == hipSuccess ? CBIM_OK : CBIM_ELAUNCH;
   }
-  if (g_stem_mfma && dtype == CBIM_BF16 && Cin == 1 && Cout % 32 == 0 && Cout <= 128) {   // matrix-core form
+  if (sw(SW_STEM_MFMA) && dtype == CBIM_BF16 && Cin == 1 && Cout % 32 == 0 && Cout <= 128) {   // matrix-core form
     const size_t tile = (size_t)p.hD * p.hH * 64 + (size_t)256 * Cout * 2, red = (size_t)4 * 32 * Cout * sizeof(float);
     const size_t sm = tile > red ? tile : red;
     dim3 grid((unsigned)(N * p.strips_per_n));
@@ -1177,14 +1170,6 @@ extern "C" int cbim_head_fwd(int dtype, const void* x, const float* w, const flo
   return CBIM_LAST_LAUNCH() == hipSuccess ? CBIM_OK : CBIM_ELAUNCH;
 }
 
-static int g_head_mfma = 1;
-/* process-wide switch (tests, A/B): 0 = the VALU head backward also where the matrix-core kernel applies; returns the old value */
-extern "C" int cbim_head_mfma_enable(int on) {
-  const int old = g_head_mfma;
-  g_head_mfma = on ? 1 : 0;
-  return old;
-}
-
 static int head_bwd_blocks(int64_t S) {
   int64_t b = (S + 4095) / 4096;
   if (b > 512) b = 512;
@@ -1210,7 +1195,7 @@ extern "C" int cbim_head_bwd(int dtype, const void* x, const float* w, const flo
     const int cpc = dtype == CBIM_BF16 ? 8 : 4, cch = Cin / cpc;
     // (bf16: one chunk per wave — two would need 2 x 16 x 8 accumulators + as many weight registers per lane: spills;
     //  wider rows, e.g. MedFormer's aux head on 128 channels, run as blockIdx.z groups of 4 chunks)
-    if (K <= 16 && g_head_mfma && dtype == CBIM_BF16 && Cin % 16 == 0 && Cin <= 128 && S % 32 == 0) {
+    if (K <= 16 && sw(SW_HEAD_MFMA) && dtype == CBIM_BF16 && Cin % 16 == 0 && Cin <= 128 && S % 32 == 0) {
       // matrix-core form (k_head_bwd_mfma): workgroups of 8 waves x 32-voxel steps, two per CU at full size
       int nb = head_bwd_blocks(S);
       int64_t vpb = (S + nb - 1) / nb;

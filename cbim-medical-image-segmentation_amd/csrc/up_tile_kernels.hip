@@ -21,6 +21,7 @@
 // host side falls back — both paths are tested against each other bit for bit).
 #include "cbim_common.h"
 #include "gfx950_prims.h"
+#include "cbim_switches.h"
 #include "up_lerp.h"
 
 namespace cbim {
@@ -239,12 +240,6 @@ extern "C" int cbim_stats_finalize(const float* partials, int N, int P, int C, d
                                    float* out, void* stream);
 
 static constexpr size_t UP_LDS_CAP = 96 * 1024;      // leaves room for a second workgroup on the CU
-static int64_t g_up_tile_min = 512;                  // fewest fine tiles per image the tiled kernels take (0: any; tests)
-extern "C" int64_t cbim_up_tile_min_tiles(int64_t v) {
-  const int64_t old = g_up_tile_min;
-  if (v >= 0) g_up_tile_min = v;
-  return old;
-}
 
 // largest coarse-box extent along one axis over all fine tiles of length t: the kernel's own index arithmetic (float
 // scale, truncation) replayed on the host
@@ -277,7 +272,8 @@ static int up_fill(UpTileParams& p, int dtype, int Dl, int Hl, int Wl, int Cl, i
   CBIM_CHECK(need <= UP_LDS_CAP, CBIM_EUNSUPPORTED, "up tile: coarse box of %dx%dx%d rows x %d channels exceeds the LDS budget", p.bd, p.bh, p.bw, Cl);
   // a workgroup per 4x8x8 fine tile: below ~512 tiles the chip is under-filled and the wide rows of the low levels leave a
   // thread 50-100 serial items (measured 75-115 us against 11-29 us of the gather kernels at 32^3 / 16^3)
-  CBIM_CHECK(g_up_tile_min <= 0 || (int64_t)p.tiles_d * p.tiles_h * p.tiles_w >= g_up_tile_min, CBIM_EUNSUPPORTED,
+  const int64_t min_tiles = sw(SW_UP_TILE_MIN_TILES);
+  CBIM_CHECK(min_tiles <= 0 || (int64_t)p.tiles_d * p.tiles_h * p.tiles_w >= min_tiles, CBIM_EUNSUPPORTED,
              "up tile: %d tiles are too few for the tiled kernels", p.tiles_d * p.tiles_h * p.tiles_w);
   *smem = need;
   return CBIM_OK;

@@ -10,6 +10,9 @@
  *  - Plain pointers and sizes only.  Every pointer is DEVICE memory owned by the caller
  *    (PyTorch caching allocator); kernels never allocate, free or retain pointers.
  *  - Launch-only and asynchronous on `stream` (a hipStream_t passed as void*); re-entrant.
+ *  - The only process-wide state is the kernel-selection switches behind the cbim_*_enable / cbim_*_min_* / cbim_*_tile_depth /
+ *    cbim_*_waves setters below: relaxed atomics, safe to flip while other threads launch, meant for tests and A/B tools
+ *    (one table: csrc/cbim_switches.h; INTEGRATION.md "Knobs").
  *  - Activations are channels-last NDHWC: element (n,d,h,w,c) of a tensor view lives at
  *    ptr[((n*D+d)*H+h)*W+w) * row_stride + c]; `row_stride` (in elements) lets a view address
  *    a channel slice of a wider tensor.  dtype: CBIM_F32 or CBIM_BF16.  Channel counts must be
