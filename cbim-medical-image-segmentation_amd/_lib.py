@@ -130,6 +130,9 @@ _SIGS = {
     "cbim_focal_workspace": (sz, [i32, i32, i64]),
     "cbim_focal_fwd": (i32, [vp, vp, vp, f32, i32, i32, i32, i64, vp, vp, vp, sz, vp]),
     "cbim_focal_bwd": (i32, [vp, vp, vp, vp, vp, vp, f32, i32, i32, i32, i64, vp]),
+    "cbim_topk_workspace": (sz, [i32, i32, i64]),
+    "cbim_topk_fwd": (i32, [vp, vp, vp, i64, i32, i32, i32, i64, vp, vp, vp, sz, vp]),
+    "cbim_topk_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, vp, vp]),
     "cbim_affine_sample3d": (i32, [vp, vp, i32, vp, vp, vp] + [i32] * 10 + [vp]),
     "cbim_crop3d": (i32, [vp, vp, i32, vp, vp] + [i32] * 10 + [vp]),
     "cbim_chan_stats_workspace": (sz, [i32, i64]),

@@ -17,6 +17,7 @@
 //                           k_resample3d<LINEAR> once, then per class the same trilinear sum (each tap optionally divided by the
 //                           window count) and a running first maximum — the K resampled volumes are never written
 #include "cbim_common.h"
+#include "radix_select.h"   // os_key / os_unkey, os_narrow: shared with topk_kernels.hip
 
 #include <string.h>
 
@@ -27,15 +28,6 @@ static constexpr int PR_T = 256;
 // ---- order statistics ------------------------------------------------------------------------------------------------------
 static constexpr int OS_MAXR = 4;
 struct OsRanks { unsigned r[OS_MAXR]; };
-
-// ascending unsigned keys <=> ascending floats (-0 sorts right below +0)
-__device__ __forceinline__ unsigned os_key(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float os_unkey(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 // workspace: unsigned hist[4][OS_MAXR][256] | prefix[OS_MAXR] | remaining[OS_MAXR]
 __global__ void __launch_bounds__(PR_T) k_os_init(unsigned* __restrict__ ws, OsRanks ranks) {
@@ -107,13 +99,8 @@ __global__ void __launch_bounds__(64) k_os_pick(unsigned* __restrict__ ws, int p
   unsigned* prefix = ws + 4 * OS_MAXR * 256;
   unsigned* remaining = prefix + OS_MAXR;
   unsigned rem = remaining[j];
-  int d = 0;
-  for (; d < 255; ++d) {
-    const unsigned c = hist[d];
-    if (rem < c) break;
-    rem -= c;
-  }
-  const unsigned p = (prefix[j] << 8) | (unsigned)d;
+  const unsigned d = os_narrow(hist, rem);
+  const unsigned p = (prefix[j] << 8) | d;
   prefix[j] = p;
   remaining[j] = rem;
   if (pass == 3) out[j] = os_unkey(p);

@@ -490,6 +490,47 @@ class FocalFn(torch.autograd.Function):
         return dz, None, None, None, None
 
 
+def topk_count(n_vox, k):
+    """K = int(n_vox * k / 100) voxels of the hardest k percent (nnU-Net's rule); refuses k outside (0, 100] and K < 1."""
+    k = float(k)
+    if not 0.0 < k <= 100.0:
+        raise ValueError(f"cbim_amd: k must lie in (0, 100] percent (got {k})")
+    K = int(n_vox * k / 100)
+    if K < 1:
+        raise ValueError(f"cbim_amd: k = {k} percent of {n_vox} voxels keeps no voxel")
+    return K
+
+
+class TopKCEFn(torch.autograd.Function):
+    """(top-k CE + Dice, top-k CE, Dice, #bad labels, top-k CE + Dice as a float32 sum) in one pass over the logits: the weighted
+    cross entropy averaged over the hardest ``k`` percent of the batch's voxels (nnU-Net's TopKLoss) [+ DiceLoss]; labels [B, ...] or
+    [B, 1, ...].  The threshold is found on the device (radix select, no sort, no synchronisation); voxels tied at it share the
+    remaining weight evenly, so value and gradient are deterministic.  The Dice entry is 0 without ``with_dice``."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, k, with_dice):
+        logits = logits.contiguous().float()
+        labels = labels.contiguous()
+        if labels.dtype != torch.int64:
+            labels = labels.long()
+        n_vox = logits.numel() // int(logits.shape[1])
+        if labels.numel() != n_vox:
+            raise ValueError(f"cbim_amd: {labels.numel()} labels for {n_vox} voxels")
+        out, coef, ws = ops.topk_fwd(logits, labels, weight, topk_count(n_vox, k), with_dice)
+        _count_bad_labels(out, logits)
+        empty = torch.empty(0)
+        ctx.save_for_backward(logits, labels, coef if coef is not None else empty, weight if weight is not None else empty, ws)
+        ctx.has_w, ctx.with_dice = weight is not None, bool(with_dice)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, labels, coef, weight, ws = ctx.saved_tensors
+        g2 = gout[1:3].float() + (gout[0] + gout[4])       # (g_topk, g_dice): entries 0 and 4 are the sum of the two terms
+        dz = ops.topk_bwd(logits, labels, weight if ctx.has_w else None, coef if ctx.with_dice else None, g2, ws, ctx.with_dice)
+        return dz, None, None, None, None
+
+
 class DicePerClassFn(torch.autograd.Function):
     """DiceLoss(reduce=False): the vector of per-class terms 1 - dice_c (training/losses.py:48-50).  The mean Dice loss is linear
     in the per-class coefficients the forward kernel leaves for the backward (coef[c] = -d dice_c / dTP_c / C, ...), so an

@@ -890,6 +890,46 @@ def focal_bwd(logits, labels, alpha, coef, grad2, gamma=2.0, with_dice=False):
     return dz
 
 
+def _topk_dtypes(logits, labels, *f32):
+    if logits.dtype != torch.float32 or labels.dtype != torch.int64 or any(t is not None and t.dtype != torch.float32 for t in f32):
+        raise TypeError("cbim_amd: the top-k loss kernels take float32 logits, weights, coefficients and gradients and int64 labels")
+
+
+def topk_fwd(logits, labels, weight=None, K=None, with_dice=False):
+    """Top-k cross entropy over the K largest per-voxel terms of the batch (K = None: all N*S, the mean CE).
+    -> out float32[5] = (top-k + Dice, top-k term, Dice (0 unless with_dice), #labels outside [0,C), top-k + Dice as a float32 sum),
+    coef: float32[3C+1] laid out as dice_ce_fwd's with with_dice (coef[2C] = 1/K), else None,
+    ws: the workspace holding the per-voxel terms and the threshold record; topk_bwd reads it."""
+    _dev_ok(logits, labels, weight)
+    _topk_dtypes(logits, labels, weight)
+    N, Cc = int(logits.shape[0]), int(logits.shape[1])
+    S = logits.numel() // (N * Cc)
+    K = N * S if K is None else int(K)
+    L = _lib.lib()
+    nbytes = L.cbim_topk_workspace(N, Cc, S)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=logits.device)
+    out = torch.empty((5,), dtype=torch.float32, device=logits.device)
+    coef = torch.empty((3 * Cc + 1,), dtype=torch.float32, device=logits.device) if with_dice else None
+    check(L.cbim_topk_fwd(_p(logits), _p(labels), _p(weight), K, int(bool(with_dice)), N, Cc, S, _p(out), _p(coef), _p(ws),
+                          nbytes, _stream(logits)), "topk_fwd")
+    return out, coef, ws
+
+
+def topk_bwd(logits, labels, weight, coef, grad2, ws, with_dice=False):
+    """grad2 float32[2] on the device: the gradients of the top-k term and of the Dice term; ws as topk_fwd left it."""
+    _dev_ok(logits, labels, weight, coef, grad2, ws)
+    _topk_dtypes(logits, labels, weight, coef, grad2)
+    N, Cc = int(logits.shape[0]), int(logits.shape[1])
+    S = logits.numel() // (N * Cc)
+    L = _lib.lib()
+    if ws.dtype != torch.uint8 or ws.numel() != L.cbim_topk_workspace(N, Cc, S):
+        raise ValueError(f"cbim_amd: topk_bwd needs the {L.cbim_topk_workspace(N, Cc, S)}-byte workspace of topk_fwd")
+    dz = torch.empty_like(logits)
+    check(L.cbim_topk_bwd(_p(logits), _p(labels), _p(weight), _p(coef), _p(grad2), _p(dz), int(bool(with_dice)), N, Cc, S,
+                          _p(ws), _stream(logits)), "topk_bwd")
+    return dz
+
+
 def ncdhw_to_ndhwc(x: torch.Tensor, dtype: torch.dtype):
     _dev_ok(x)
     N, Cc = int(x.shape[0]), int(x.shape[1])

@@ -1,5 +1,5 @@
 """Loss modules with the reference's call surface (/root/reference/training/losses.py:8-98,
-/root/reference/train.py:80-81,212), computed by the fused HIP Dice+CE and focal kernels."""
+/root/reference/train.py:80-81,212), computed by the fused HIP Dice+CE and focal kernels, and the top-k cross entropy (hard-example mining) on the same kernel family."""
 import torch
 import torch.nn as nn
 
@@ -82,6 +82,42 @@ class DiceFocalLoss(nn.Module):
         with torch.autocast(device_type=logits.device.type, enabled=False):
             out = Fn.FocalFn.apply(logits, label, self.alpha, self.gamma, True)
             return out[4]
+
+
+def _topk_args(weight, k):
+    k = float(k)
+    if not 0.0 < k <= 100.0:
+        raise ValueError(f"k must lie in (0, 100] percent (got {k})")
+    return (None if weight is None else torch.as_tensor(weight, dtype=torch.float32).detach().clone().reshape(-1)), k
+
+
+class TopKLoss(nn.Module):
+    """TopKLoss(weight, k)(preds[B,C,...], targets[B,...] or [B,1,...] int64): nn.CrossEntropyLoss(weight, reduction="none")
+    averaged over the hardest ``k`` percent of all voxels of the batch — K = int(B*S*k/100) of them, the sum of the K largest
+    terms divided by K (nnU-Net's TopKLoss; k = 100 is the mean cross entropy).  Voxels tied at the threshold share evenly."""
+
+    def __init__(self, weight=None, k=10):
+        super().__init__()
+        weight, self.k = _topk_args(weight, k)
+        self.register_buffer("weight", weight)
+
+    def forward(self, preds, targets):
+        with torch.autocast(device_type=preds.device.type, enabled=False):
+            return Fn.TopKCEFn.apply(preds, targets, self.weight, self.k, False)[1]
+
+
+class DiceTopKLoss(nn.Module):
+    """TopKLoss(weight, k)(logits, label) + DiceLoss()(logits, label) in one pass (nnU-Net's DC_and_topk_loss recipe) as a drop-in
+    for DiceCELoss (label [B,1,...]; summed over the outputs of a deep-supervision net like it)."""
+
+    def __init__(self, weight=None, k=10):
+        super().__init__()
+        weight, self.k = _topk_args(weight, k)
+        self.register_buffer("weight", weight)
+
+    def forward(self, logits, label):
+        with torch.autocast(device_type=logits.device.type, enabled=False):
+            return Fn.TopKCEFn.apply(logits, label, self.weight, self.k, True)[4]
 
 
 def check_labels(reset: bool = True) -> int:

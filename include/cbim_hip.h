@@ -378,6 +378,30 @@ int cbim_focal_bwd(const float* logits, const int64_t* labels, const float* alph
                    void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Loss: top-k cross entropy (online hard-example mining, nnU-Net's TopKLoss) [+ DiceLoss()(logits, label)] in one read of
+ * the logits; tensors as above, C <= 32, N*S <= 2^31.
+ * Per voxel nll = weight[y] * (logsumexp(z) - z[y]) (weight float [C] or NULL: all ones); the term is the sum of the K largest
+ * nll of the whole batch divided by K (not by a sum of weights), 1 <= K <= N*S (K = N*S: the mean CE).  With tau the K-th
+ * largest value, n_gt = #{nll > tau}, n_eq = #{nll == tau}: term = (sum_{nll > tau} nll + (K - n_gt) tau) / K, and a voxel's share
+ * of the gradient is 1/K above tau, (K - n_gt) / (n_eq K) at tau, 0 below (ties share evenly: deterministic).  tau comes from an
+ * exact radix select on the device: no sort, no host synchronisation, integer atomics only (bitwise reproducible).
+ * fwd: out float[5]: out[0]=top-k term + Dice, out[1]=top-k term, out[2]=Dice (0 unless with_dice), out[3]=number of labels
+ *      outside [0,C) (handled as in the CE + Dice entry points: excluded, counted; they take part in the selection with nll = 0
+ *      and K is not reduced), out[4]=out[1]+out[2] in float32.  with_dice != 0: the Dice term is that of the CE + Dice entry
+ *      points bit for bit and coef float [3C + 1] is laid out like theirs ([2][C] class coefficients, coef[2C] = 1/K, [C]
+ *      per-class terms); with_dice == 0: coef may be NULL.  workspace: cbim_topk_workspace(N,C,S) bytes, 16-byte aligned; it
+ *      holds the per-voxel nll and the record (tau, 1/K, tie share) that bwd reads: pass the SAME, untouched workspace to bwd.
+ * bwd: dlogits = grad_out[0] * d out[1]/dlogits + grad_out[1] * d out[2]/dlogits (grad_out: DEVICE float[2]; grad_out[1] is
+ *      not read unless with_dice).
+ * ------------------------------------------------------------------------------------------ */
+size_t cbim_topk_workspace(int N, int C, int64_t S);
+int cbim_topk_fwd(const float* logits, const int64_t* labels, const float* weight, int64_t K, int with_dice, int N,
+                  int C, int64_t S, float* out, float* coef, void* workspace, size_t ws_bytes, void* stream);
+int cbim_topk_bwd(const float* logits, const int64_t* labels, const float* weight, const float* coef,
+                  const float* grad_out, float* dlogits, int with_dice, int N, int C, int64_t S,
+                  const void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device augmentation — training/augmentation.py (tensor_img [1,C,D,H,W] fp32, tensor_lab
  * [1,1,D,H,W] int8|int64), called per sample from the dataset (training/dataset/dim3/
  * dataset_amos_ct.py:121-153).  Random parameters are drawn by the HOST in the reference's order.
