@@ -8,6 +8,14 @@ iteration (``csrc/optim_kernels.hip``).
 ``update_ema_variables(model, ema_model, alpha, global_step)`` into the same launch; its buffers are copied as
 the reference does (the shipped nets have none).  One parameter group, fp32 parameters on the GPU; anything
 else raises.
+
+``max_grad_norm`` folds ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm)`` into the step, and the optimizer speaks
+``torch.amp.GradScaler``'s protocol for fused optimizers (``_step_supports_amp_scaling``: the scaler hands over the device
+tensors ``grad_scale`` / ``found_inf`` and the step unscales and skips by itself): global norm, clip coefficient, unscale
+and the skip decision are computed on the device (``cbim_adamw_ema_step_guarded``), with no host round trip, so the step
+stays capturable in a graph.  Two differences from torch: ``p.grad`` is NOT rewritten (it keeps the scaled, unclipped
+gradient of ``backward()``), and a step whose gradient norm is not finite is skipped — weights, moments, EMA and the step
+counter untouched, ``skipped_steps`` counted — where torch without a scaler would write NaN weights.
 """
 from __future__ import annotations
 
@@ -25,8 +33,12 @@ class _Rec(C.Structure):
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, ema_model=None, ema_alpha=0.99):
-        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+    _step_supports_amp_scaling = True      # torch.amp.GradScaler.step: hand grad_scale / found_inf over, do not unscale or sync
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, ema_model=None, ema_alpha=0.99,
+                 max_grad_norm=None):
+        self._max_norm_value({"max_grad_norm": max_grad_norm})
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
         super().__init__(params, defaults)
         if len(self.param_groups) != 1:
             raise NotImplementedError("cbim_amd: FusedAdamW supports one parameter group")
@@ -49,6 +61,19 @@ class FusedAdamW(torch.optim.Optimizer):
         self._ptrs = None
         self._hyper = None
         self._lr_pushed = None
+        self._partial = None
+        self._ctl = None
+
+    @property
+    def grad_norm(self):
+        """0-d device tensor: global L2 norm of the (unscaled) gradients of the last guarded step; no host sync.  ``None`` before
+        the first step; a step that ran unguarded (no ``max_grad_norm``, no scaler) does not update it."""
+        return None if self._ctl is None else self._ctl[0]
+
+    @property
+    def skipped_steps(self):
+        """0-d device tensor: how many steps were skipped so far (non-finite gradient norm or the scaler's ``found_inf``)."""
+        return None if self._ctl is None else self._ctl[3]
 
     # -- state (torch.optim.AdamW layout) ---------------------------------------------------------------
     def _init_state(self):
@@ -73,8 +98,15 @@ class FusedAdamW(torch.optim.Optimizer):
         g = self.param_groups[0]
         step0 = float(self.state[self._params[0]]["step"])
         self._hyper = torch.tensor([step0, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
-                                    self.ema_alpha, 0.0, 1.0 - g["betas"][0], 1.0 - g["betas"][1]], dtype=torch.float32,
-                                   device=dev)
+                                    self.ema_alpha, self._max_norm_value(g), 1.0 - g["betas"][0], 1.0 - g["betas"][1]],
+                                   dtype=torch.float32, device=dev)
+        # the guarded step's scratch (one float per block) and control block {norm, mult, skip, skipped}; the count of skipped
+        # steps survives a rebuild of the table
+        skipped = self._ctl[3].clone() if self._ctl is not None else None
+        self._partial = torch.zeros((self._nblocks,), dtype=torch.float32, device=dev)
+        self._ctl = torch.zeros((4,), dtype=torch.float32, device=dev)
+        if skipped is not None:
+            self._ctl[3] = skipped
         self._lr_pushed = self._hyper_key(g)
         # pinned staging buffers, allocated up front (no host allocation may happen while a hipGraph is being
         # captured) and used round-robin: a captured graph re-reads the buffer it was recorded with on replay
@@ -130,13 +162,28 @@ class FusedAdamW(torch.optim.Optimizer):
         if key != self._lr_pushed:              # the scheduler changed the learning rate (training/utils.py:51-95), or the
             # user edited betas / eps / weight_decay in param_groups: push the whole tuple (one small H2D copy; under a
             # captured graph the step is replayed with the values captured — edit them between captures)
-            vals = torch.tensor([key[0], key[1], key[2], key[3], key[4], 1.0 - key[1], 1.0 - key[2]], dtype=torch.float32)
-            self._hyper[1:6] = vals[:5].to(self._hyper.device)
-            self._hyper[8:10] = vals[5:].to(self._hyper.device)
+            if key[:5] != self._lr_pushed[:5]:
+                vals = torch.tensor([key[0], key[1], key[2], key[3], key[4], 1.0 - key[1], 1.0 - key[2]], dtype=torch.float32)
+                self._hyper[1:6] = vals[:5].to(self._hyper.device)
+                self._hyper[8:10] = vals[5:].to(self._hyper.device)
+            if key[5] != self._lr_pushed[5]:    # max_grad_norm edited in param_groups
+                self._hyper[7:8] = torch.tensor([key[5]], dtype=torch.float32).to(self._hyper.device)
             self._lr_pushed = key
         self._fill_table()
-        _lib.check(_lib.lib().cbim_adamw_ema_step(_p(self._table), _p(self._blk_tensor), _p(self._blk_chunk), self._nblocks,
-                                                  _p(self._hyper), _stream(self._params[0])), "adamw_ema_step")
+        # torch.amp.GradScaler.step sets these two before the call and deletes them after it; grad_scale is None when the user
+        # ran scaler.unscale_ (to look at the gradients) first
+        grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
+        if g.get("max_grad_norm") is None and grad_scale is None and found_inf is None:
+            _lib.check(_lib.lib().cbim_adamw_ema_step(_p(self._table), _p(self._blk_tensor), _p(self._blk_chunk), self._nblocks,
+                                                      _p(self._hyper), _stream(self._params[0])), "adamw_ema_step")
+        else:
+            for name, t in (("grad_scale", grad_scale), ("found_inf", found_inf)):
+                if t is not None and (t.dtype != torch.float32 or t.numel() != 1 or t.device != self._hyper.device):
+                    raise RuntimeError(f"cbim_amd: FusedAdamW.{name} must be a one-element fp32 tensor on the parameters' device")
+            _lib.check(_lib.lib().cbim_adamw_ema_step_guarded(
+                _p(self._table), _p(self._blk_tensor), _p(self._blk_chunk), self._nblocks, _p(self._hyper), _p(self._partial),
+                _p(self._ctl), _p(grad_scale) if grad_scale is not None else None,
+                _p(found_inf) if found_inf is not None else None, _stream(self._params[0])), "adamw_ema_step_guarded")
         # the kernel wrote the parameters (and the EMA copies) through raw pointers: tell autograd / every cache keyed on
         # Tensor._version (ops.PackedWeights: packed convolution weights) that they changed
         torch.autograd.graph.increment_version(self._params)
@@ -148,8 +195,20 @@ class FusedAdamW(torch.optim.Optimizer):
         return loss
 
     @staticmethod
+    def _max_norm_value(g):
+        """hyper[7]: 0 = do not clip (``max_grad_norm=None``; a checkpoint from before the option has no such key)."""
+        m = g.get("max_grad_norm")
+        if m is None:
+            return 0.0
+        m = float(m)
+        if not m > 0.0:
+            raise ValueError(f"cbim_amd: FusedAdamW max_grad_norm must be positive or None, got {m}")
+        return m
+
+    @staticmethod
     def _hyper_key(g):
-        return (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
+        return (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                FusedAdamW._max_norm_value(g))
 
     def _model_buffers(self):
         src = getattr(self, "_buffers_src", None)
@@ -190,7 +249,8 @@ def get_optimizer(args, net, ema_net=None):
     if args.optimizer != "adamw":
         return None    # the reference falls through the same way
     opt = FusedAdamW(net.parameters(), lr=args.base_lr, betas=args.betas, weight_decay=args.weight_decay, eps=1e-5,
-                     ema_model=ema_net, ema_alpha=getattr(args, "ema_alpha", 0.99))
+                     ema_model=ema_net, ema_alpha=getattr(args, "ema_alpha", 0.99),
+                     max_grad_norm=getattr(args, "max_grad_norm", None))
     if ema_net is not None:
         opt.attach_buffers(net)
     return opt

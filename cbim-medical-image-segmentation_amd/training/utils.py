@@ -20,7 +20,8 @@ from .. import _lib
 from ..ops import _p, _stream
 from .optim import FusedAdamW, _Rec
 
-__all__ = ["get_optimizer", "update_ema_variables", "exp_lr_scheduler_with_warmup", "multistep_lr_scheduler_with_warmup"]
+__all__ = ["get_optimizer", "grad_norm", "update_ema_variables", "exp_lr_scheduler_with_warmup",
+           "multistep_lr_scheduler_with_warmup"]
 
 
 def get_optimizer(args, net):
@@ -31,8 +32,43 @@ def get_optimizer(args, net):
     if args.optimizer == "adam":
         return optim.Adam(net.parameters(), lr=args.base_lr, betas=args.betas, weight_decay=args.weight_decay)
     if args.optimizer == "adamw":
-        return FusedAdamW(net.parameters(), lr=args.base_lr, betas=tuple(args.betas), weight_decay=args.weight_decay, eps=1e-5)
+        return FusedAdamW(net.parameters(), lr=args.base_lr, betas=tuple(args.betas), weight_decay=args.weight_decay, eps=1e-5,
+                          max_grad_norm=getattr(args, "max_grad_norm", None))
     return None    # the reference falls through the same way
+
+
+@torch.no_grad()
+def grad_norm(parameters):
+    """Global L2 norm of the gradients of ``parameters`` as a 0-d device tensor (``cbim_grad_norm``: the two reduction kernels
+    of the guarded FusedAdamW step alone), for logging; parameters without a gradient are left out, as
+    ``torch.nn.utils.clip_grad_norm_`` leaves them out.  The value is bitwise reproducible (fixed summation order)."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        raise ValueError("cbim_amd: grad_norm: no parameter has a gradient")
+    dev = grads[0].device
+    for g in grads:
+        if g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev:
+            raise RuntimeError("cbim_amd: grad_norm needs contiguous fp32 gradients on one device")
+    chunk = _lib.lib().cbim_optim_chunk()
+    bt, bc = [], []
+    for i, g in enumerate(grads):
+        n = (g.numel() + chunk - 1) // chunk
+        bt += [i] * n
+        bc += list(range(n))
+    host = torch.empty((len(grads) * C.sizeof(_Rec),), dtype=torch.uint8)
+    recs = (_Rec * len(grads)).from_address(host.data_ptr())
+    for i, g in enumerate(grads):
+        recs[i] = _Rec(None, g.data_ptr(), None, None, None, g.numel())
+    table = host.to(dev)
+    blk_tensor = torch.tensor(bt, dtype=torch.int32, device=dev)
+    blk_chunk = torch.tensor(bc, dtype=torch.int32, device=dev)
+    partial = torch.empty((len(bt),), dtype=torch.float32, device=dev)
+    out = torch.zeros((1,), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().cbim_grad_norm(_p(table), _p(blk_tensor), _p(blk_chunk), len(bt), _p(partial), _p(out),
+                                         _stream(grads[0])), "grad_norm")
+    return out[0]
 
 
 class _EmaTable:

@@ -594,7 +594,8 @@ int cbim_window_attn3d_bwd(int dtype, const void* qkv, const float* qkv_bias, co
  *   tensors   : DEVICE array of records (fp32 parameter, gradient, exp_avg, exp_avg_sq, ema copy or NULL)
  *   blk_tensor/blk_chunk : DEVICE int32[nblocks]: workgroup b updates elements [chunk*C, chunk*C + C) of tensor
  *               blk_tensor[b], C = cbim_optim_chunk()
- *   hyper     : DEVICE float[10] = {step, lr, beta1, beta2, eps, weight_decay, ema_alpha, 0, 1-beta1, 1-beta2};
+ *   hyper     : DEVICE float[10] = {step, lr, beta1, beta2, eps, weight_decay, ema_alpha, max_grad_norm, 1-beta1, 1-beta2}
+ *               (max_grad_norm is read by cbim_adamw_ema_step_guarded alone);
  *               the call first
  *               increments hyper[0] on the device (graph-capturable), then applies torch's AdamW update with
  *               bias corrections for that step, then ema = a*ema + (1-a)*p with a = min(1 - 1/step, ema_alpha).
@@ -610,6 +611,24 @@ typedef struct {
 int cbim_optim_chunk(void);
 int cbim_adamw_ema_step(const cbim_optim_tensor* tensors, const int32_t* blk_tensor, const int32_t* blk_chunk,
                         int nblocks, float* hyper, void* stream);
+/* The same step with what a training loop does around optimizer.step() folded in: torch.nn.utils.clip_grad_norm_ (global L2
+ * norm), the unscale of torch.amp.GradScaler and the skip of a step whose gradients are not finite.  Three launches, no host
+ * round trip (graph-capturable), one more read of the gradients and NO write to them:
+ *   1. partial[b] = sum over block b's chunk of (g / *grad_scale)^2 in fp32 (unscaled before squaring; fixed order, no atomics:
+ *      bitwise reproducible; gradients at any 4-byte aligned address);
+ *   2. one workgroup adds partial[0..nblocks) in double and writes ctl = {norm, mult, skip, skipped}:
+ *        norm = L2 norm of the unscaled gradients;  mult = (1 / *grad_scale) * min(1, max_norm / (norm + 1e-6)) with
+ *        max_norm = hyper[7] (<= 0 or inf: no clipping, the coefficient is exactly 1);  skip = 1 when norm is not finite or
+ *        *found_inf > 0;  skipped += skip (the caller zeroes ctl once).  hyper[0] is incremented only when skip == 0;
+ *   3. the AdamW + EMA update with g * mult in place of g; nothing at all is written when skip is set.
+ *   partial : DEVICE float[nblocks] scratch;  ctl : DEVICE float[4];  grad_scale / found_inf : DEVICE float[1] or NULL
+ *   (NULL grad_scale = scale 1, NULL found_inf = 0).  NULL partial or ctl: CBIM_EINVAL. */
+int cbim_adamw_ema_step_guarded(const cbim_optim_tensor* tensors, const int32_t* blk_tensor, const int32_t* blk_chunk,
+                                int nblocks, float* hyper, float* partial, float* ctl, const float* grad_scale,
+                                const float* found_inf, void* stream);
+/* Launches 1 and 2 alone, for logging: out[0] = L2 norm over every record's gradient (.g, .numel used). */
+int cbim_grad_norm(const cbim_optim_tensor* tensors, const int32_t* blk_tensor, const int32_t* blk_chunk, int nblocks,
+                   float* partial, float* out, void* stream);
 /* update_ema_variables alone (/root/reference/training/utils.py:98-102, called at train.py:218) for callers that keep
  * another optimizer: ema = alpha*ema + (1-alpha)*p over every record (.p, .ema, .numel used) in one launch; alpha is
  * the already clamped min(1 - 1/(global_step+1), ema_alpha), one_minus_alpha = (float)(1 - (double)alpha) as torch
