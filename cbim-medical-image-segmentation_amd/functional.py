@@ -312,6 +312,7 @@ class UpBlockFirstFn(_GradAwareFunction):
     @staticmethod
     def forward(ctx, low, skip, skip_stats, w1, w2, wsc, act, want_out_stats, skip_first):
         train = _training(ctx)
+        low, skip = low.contiguous(), skip.contiguous()     # the up-path kernels read both as dense memory
         up_st = ops.up_stats(low, skip.shape[1:4])
         stats_cat = torch.cat([skip_stats, up_st] if skip_first else [up_st, skip_stats], 1)
         a = ops.upcat_act_fwd(low, skip, stats_cat, act, skip_first)
@@ -363,7 +364,7 @@ class MaxPoolFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, scale):
-        y, idx = ops.maxpool_fwd(x, scale)
+        y, idx = ops.maxpool_fwd(x.contiguous(), scale)
         ctx.save_for_backward(idx)
         ctx.in_shape, ctx.scale = tuple(x.shape), tuple(scale)
         return y
@@ -380,6 +381,7 @@ class UpCatFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, low, skip, skip_first, want_stats=False):
         ctx.low_shape, ctx.Cs, ctx.skip_first = tuple(low.shape), int(skip.shape[-1]), skip_first
+        low, skip = low.contiguous(), skip.contiguous()
         if want_stats:   # statistics of the concatenated tensor from the same pass (non-differentiable output)
             out, st = ops.upcat_fwd_stats(low, skip, skip_first)
             ctx.mark_non_differentiable(st)
@@ -399,6 +401,7 @@ class HeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b):
         w2d = w.detach().reshape(w.shape[0], w.shape[1]).contiguous()
+        x = x.contiguous()
         ctx.save_for_backward(x, w2d)
         ctx.w_shape, ctx.w_param, ctx.b_param = tuple(w.shape), ops.slot_of(w), ops.slot_of(b)
         return ops.head_fwd(x, w2d, b.detach().contiguous())
@@ -735,7 +738,7 @@ class SpaceToDepthFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, scale):
         ctx.in_shape, ctx.scale = tuple(x.shape), tuple(scale)
-        return ops.space_to_depth(x, scale)
+        return ops.space_to_depth(x.contiguous(), scale)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1052,7 +1055,7 @@ class DepthToSpaceFn(torch.autograd.Function):
         N, D, H, W, Cm = map(int, t.shape)
         sD, sH, sW = scale
         ctx.scale = tuple(scale)
-        return ops.depth_to_space(t, (N, D * sD, H * sH, W * sW, Cm // (sD * sH * sW)), scale)
+        return ops.depth_to_space(t.contiguous(), (N, D * sD, H * sH, W * sW, Cm // (sD * sH * sW)), scale)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1362,6 +1365,7 @@ class GateFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, psi):
         psi = psi.contiguous().float()
+        x = x.contiguous()
         ctx.save_for_backward(x, psi)
         return ops.gate_fwd(x, psi)
 

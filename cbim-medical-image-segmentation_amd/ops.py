@@ -35,32 +35,78 @@ def _dt(t: torch.Tensor) -> int:
     raise TypeError(f"cbim_amd: unsupported activation dtype {t.dtype}")
 
 
-def _dev_ok(*ts):
+def _on_device(t):
     want = "cpu" if _lib.backend() == "emu" else "cuda"
+    if t.device.type != want:
+        raise RuntimeError(
+            f"cbim_amd: tensor on '{t.device.type}' but the loaded kernel library "
+            f"({_lib.backend()}) executes on '{want}' — there is no fallback path")
+
+
+def _dev_ok(*ts):
+    """every operand the library reads or writes as DENSE memory: on the executing device and contiguous"""
     for t in ts:
         if t is None:
             continue
-        if t.device.type != want:
-            raise RuntimeError(
-                f"cbim_amd: tensor on '{t.device.type}' but the loaded kernel library "
-                f"({_lib.backend()}) executes on '{want}' — there is no fallback path")
-        if not t.is_contiguous() and not _is_row_view(t):
-            raise RuntimeError("cbim_amd: non-contiguous tensor passed to a kernel")
+        _on_device(t)
+        if not t.is_contiguous():
+            raise RuntimeError("cbim_amd: non-contiguous tensor passed to a kernel that reads it as dense memory")
+
+
+def _view_ok(*ts):
+    """_dev_ok for the channels-last operands whose row stride the call hands to the library (`_rs(t)`): besides contiguous
+    tensors, a channel range [N,D,H,W,a:b] of a wider contiguous tensor passes when the kernels' 16-byte chunks fit it"""
+    for t in ts:
+        if t is None:
+            continue
+        _on_device(t)
+        if not t.is_contiguous():
+            why = _row_view_defect(t)
+            if why is not None:
+                raise RuntimeError(f"cbim_amd: non-contiguous tensor passed to a kernel ({why})")
 
 
 def _rows_ok(*ts):
-    """_dev_ok for the token-row entry points, which take a row stride: [rows, C'] channel slices of a wider row tensor pass"""
-    _dev_ok(*[t if (t is None or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.shape[1]) else t.as_strided((1,), (1,)) for t in ts])
+    """_view_ok for the token-row entry points, which take a row stride: [rows, C'] channel slices of a wider row tensor pass"""
+    for t in ts:
+        if t is None:
+            continue
+        _on_device(t)
+        if not t.is_contiguous():
+            why = "not a [rows, C'] channel range of a wider row tensor" if (t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.shape[1]) \
+                else _chunk_defect(t, int(t.stride(0)))
+            if why is not None:
+                raise RuntimeError(f"cbim_amd: non-contiguous tensor passed to a kernel ({why})")
+
+
+def _chunk_defect(t: torch.Tensor, row_stride: int):
+    """why the kernels' 16-byte loads and stores cannot address the rows of the channel-range view t (None: they can)"""
+    es = t.element_size()
+    if t.data_ptr() % 16:
+        return "the channel range does not start on a 16-byte boundary"
+    if (row_stride * es) % 16:
+        return "the row stride is not a multiple of 16 bytes"
+    if (int(t.shape[-1]) * es) % 16:
+        return "the channel count is not a whole number of 16-byte chunks"
+    return None
+
+
+def _row_view_defect(t: torch.Tensor):
+    """None when t is a channels-last [N,D,H,W,C'] view that selects a channel range of a wider contiguous tensor — unit channel
+    stride, rows `row_stride` elements apart, voxels dense — which the 16-byte chunks of the kernels fit; else the reason it is not"""
+    if t.dim() != 5 or t.stride(-1) != 1:
+        return "not a channel range of a channels-last tensor"
+    rs = t.stride(3)
+    N, D, H, W, Cc = t.shape
+    # (the stride of an axis of extent 1 is never stepped over: a depth range of ONE image is dense, as for is_contiguous)
+    dense = all(n == 1 or t.stride(d) == want for d, n, want in ((2, H, W * rs), (1, D, H * W * rs), (0, N, D * H * W * rs)))
+    if rs < Cc or not dense:
+        return "the voxels of the view are not dense"
+    return _chunk_defect(t, int(rs))
 
 
 def _is_row_view(t: torch.Tensor) -> bool:
-    """channels-last [N,D,H,W,C'] view that selects a channel range of a wider contiguous tensor:
-    unit channel stride, rows `row_stride` elements apart, voxels dense."""
-    if t.dim() != 5 or t.stride(-1) != 1:
-        return False
-    rs = t.stride(3)
-    N, D, H, W, _ = t.shape
-    return t.stride(2) == W * rs and t.stride(1) == H * W * rs and t.stride(0) == D * H * W * rs
+    return _row_view_defect(t) is None
 
 
 def _rs(t: torch.Tensor) -> int:
@@ -95,7 +141,7 @@ def _spatial(x):
 # ------------------------------------------------------------------------------------------------
 
 def instnorm_stats(x: torch.Tensor, eps: float = IN_EPS) -> torch.Tensor:
-    _dev_ok(x)
+    _view_ok(x)
     N, Cc, S = int(x.shape[0]), int(x.shape[-1]), _spatial(x)
     L = _lib.lib()
     P = L.cbim_stats_parts(S, Cc)
@@ -140,7 +186,8 @@ def se_fold_bwd(sums, se, rz2, eps: float, S: int):
 
 
 def norm_act_fwd(x, stats, act: int):
-    _dev_ok(x, stats)
+    _view_ok(x)
+    _dev_ok(stats)
     N, Cc, S = int(x.shape[0]), int(x.shape[-1]), _spatial(x)
     y = torch.empty(tuple(x.shape), dtype=x.dtype, device=x.device)
     check(_lib.lib().cbim_norm_act_fwd(_dt(x), _p(x), _rs(x), _p(stats), _p(y), Cc, N, S, Cc, act, _stream(x)),
@@ -150,7 +197,8 @@ def norm_act_fwd(x, stats, act: int):
 
 def norm_bwd_sums(g, x, stats, act: int, masked: bool):
     """(mean(g'), mean(g'*xh)) per (n, c), g' = g*act'(xh) when masked."""
-    _dev_ok(g, x, stats)
+    _view_ok(g, x)
+    _dev_ok(stats)
     N, Cc, S = int(x.shape[0]), int(x.shape[-1]), _spatial(x)
     L = _lib.lib()
     P = L.cbim_stats_parts(S, Cc)
@@ -161,7 +209,8 @@ def norm_bwd_sums(g, x, stats, act: int, masked: bool):
 
 
 def norm_bwd_apply(g, x, stats, sums, act: int, masked: bool, add=None):
-    _dev_ok(g, x, stats, sums, add)
+    _view_ok(g, x, add)
+    _dev_ok(stats, sums)
     N, Cc, S = int(x.shape[0]), int(x.shape[-1]), _spatial(x)
     dx = torch.empty(tuple(x.shape), dtype=x.dtype, device=x.device)
     check(_lib.lib().cbim_norm_bwd_apply(_dt(x), _p(g), _rs(g), _p(x), _rs(x), _p(stats), _p(sums), _p(add),
@@ -172,7 +221,8 @@ def norm_bwd_apply(g, x, stats, sums, act: int, masked: bool, add=None):
 
 def norm_affine_act_fwd(x, stats, affine, act: int):
     """y = act(gamma * (x - mean) * rstd + beta); affine float32 [C, 2] = (gamma, beta)."""
-    _dev_ok(x, stats, affine)
+    _view_ok(x)
+    _dev_ok(stats, affine)
     N, Cc, S = int(x.shape[0]), int(x.shape[-1]), _spatial(x)
     y = torch.empty(tuple(x.shape), dtype=x.dtype, device=x.device)
     check(_lib.lib().cbim_norm_affine_act_fwd(_dt(x), _p(x), _rs(x), _p(stats), _p(affine), _p(y), Cc, N, S, Cc, act, _stream(x)),
@@ -182,7 +232,8 @@ def norm_affine_act_fwd(x, stats, affine, act: int):
 
 def norm_affine_bwd_sums(g, x, stats, affine, act: int, masked: bool):
     """per (n, c): (mean(g'), mean(g' * xh)), g' = g * act'(gamma xh + beta) when masked."""
-    _dev_ok(g, x, stats, affine)
+    _view_ok(g, x)
+    _dev_ok(stats, affine)
     N, Cc, S = int(x.shape[0]), int(x.shape[-1]), _spatial(x)
     L = _lib.lib()
     P = L.cbim_stats_parts(S, Cc)
@@ -194,7 +245,8 @@ def norm_affine_bwd_sums(g, x, stats, affine, act: int, masked: bool):
 
 def norm_affine_bwd_apply(g, x, stats, affine, sums, act: int, masked: bool):
     """dx = rstd * (gamma g' - m1 - xh m2), sums = (m1, m2) = gamma * (mean g', mean g' xh)."""
-    _dev_ok(g, x, stats, affine, sums)
+    _view_ok(g, x)
+    _dev_ok(stats, affine, sums)
     N, Cc, S = int(x.shape[0]), int(x.shape[-1]), _spatial(x)
     dx = torch.empty(tuple(x.shape), dtype=x.dtype, device=x.device)
     check(_lib.lib().cbim_norm_affine_bwd_apply(_dt(x), _p(g), _rs(g), _p(x), _rs(x), _p(stats), _p(affine), _p(sums), _p(dx), Cc,
@@ -620,12 +672,13 @@ def packed_weights(ws, geom: ConvGeom, need_dgrad: bool):
 def conv_igemm(desc: ConvDesc, x, w_packed, out_shape, in_stats=None, res=None, mask_x=None, mask_stats=None,
                want_partials: bool = False, x2=None, out=None):
     """x2: second input tensor; the conv's input is the channel concatenation [x | x2] (never
-    materialised), split at x.shape[-1].  out: write into this (dense) tensor instead of a new one; it may be `res`
+    materialised), split at x.shape[-1].  out: write into this tensor (dense or a channel-range view) instead of a new one; it may be `res`
     itself (in-place accumulation: every output chunk is read and written once, by the same thread)."""
-    _dev_ok(x, w_packed, in_stats, res, mask_x, mask_stats, x2, out)
+    _view_ok(x, x2, res, mask_x, out)
+    _dev_ok(w_packed, in_stats, mask_stats)
     L = _lib.lib()
     if out is not None:
-        assert tuple(out.shape) == tuple(out_shape) and out.dtype == x.dtype and out.is_contiguous()
+        assert tuple(out.shape) == tuple(out_shape) and out.dtype == x.dtype
         y = out
     else:
         y = torch.empty(tuple(out_shape), dtype=x.dtype, device=x.device)
@@ -737,7 +790,8 @@ WGRAD_EMBED_133 = True   # (1,3,3) weight gradients as the centre plane of a 3x3
 def conv_wgrad(x, in_stats, dy, geom: ConvGeom, dy2=None, x2=None, out=None) -> torch.Tensor:
     """dy2: gradient of the output channels >= dy.shape[-1] (Cout-concatenated convs); x2: the input channels
     >= x.shape[-1] (virtual concatenation, raw bf16 3x3x3 inputs only); out: where to write (ops.grad_slot)."""
-    _dev_ok(x, in_stats, dy, dy2, x2)
+    _view_ok(x, x2, dy, dy2)
+    _dev_ok(in_stats)
     if (WGRAD_EMBED_133 and geom.k == (1, 3, 3) and geom.pad == (0, 1, 1) and in_stats is None and x.dtype == torch.bfloat16
             and geom.Cin % 32 == 0 and geom.Cout % 32 == 0 and min(geom.in_dhw) >= 8):
         # round 6: the (1, 3, 3) kernels of the ACDC-structured configurations (config/acdc/*.yaml: kernel_size [[1,3,3],[1,3,3],...]) —
@@ -954,7 +1008,8 @@ def ndhwc_to_ncdhw(x: torch.Tensor):
 
 def dwconv(x, w2d, k, in_stats=None, act: int = 0, bias=None, flip: bool = False):
     """depthwise conv, stride 1, pad k//2; w2d float32 [C, kD*kH*kW]; optional fused IN(+act) on load."""
-    _dev_ok(x, w2d, in_stats, bias)
+    _view_ok(x)
+    _dev_ok(w2d, in_stats, bias)
     N, D, H, W, Cc = map(int, x.shape)
     y = torch.empty((N, D, H, W, Cc), dtype=x.dtype, device=x.device)
     check(_lib.lib().cbim_dwconv3d(_dt(x), _p(x), _rs(x), _p(in_stats), act, _p(bias), _p(w2d), int(flip), _p(y), Cc,
@@ -984,7 +1039,8 @@ def _shift_consts(device):
 
 
 def dwconv_wgrad(x, in_stats, act: int, dy, k, dy_bias=None):
-    _dev_ok(x, in_stats, dy, dy_bias)
+    _view_ok(x, dy)
+    _dev_ok(in_stats, dy_bias)
     N, D, H, W, Cc = map(int, x.shape)
     kD, kH, kW = (int(i) for i in k)
     L = _lib.lib()
@@ -1030,7 +1086,8 @@ def depth_to_space(dy, in_shape, scale):
 
 def depth_to_space_into(t, out, Cc: int, scale):
     """scatter t [N, D/s, H/s, W/s, s^3 Cc] into the first Cc channels of the wider channels-last tensor out [N, D, H, W, >= Cc]"""
-    _dev_ok(t, out)
+    _dev_ok(t)
+    _view_ok(out)
     N, D, H, W = (int(v) for v in out.shape[:4])
     sD, sH, sW = (int(i) for i in scale)
     check(_lib.lib().cbim_space_to_depth_strided(_dt(t), _p(t), _p(out), N, D, H, W, Cc, sD, sH, sW, 1, int(out.stride(3)), _stream(t)),
@@ -1040,7 +1097,7 @@ def depth_to_space_into(t, out, Cc: int, scale):
 
 def space_to_depth_from(g, Cc: int, scale):
     """gather the first Cc channels of the channels-last (row-strided) tensor g [N, D, H, W, >= Cc] into [N, D/s, H/s, W/s, s^3 Cc]"""
-    _dev_ok(g)
+    _view_ok(g)
     N, D, H, W = (int(v) for v in g.shape[:4])
     sD, sH, sW = (int(i) for i in scale)
     y = torch.empty((N, D // sD, H // sH, W // sW, Cc * sD * sH * sW), dtype=g.dtype, device=g.device)
@@ -1056,7 +1113,8 @@ def _attn_ws(N, L, heads, dh, M, dev):
 
 def bidir_attn_fwd(qv, mq, mv, heads: int, scale: float):
     """qv [N,D,H,W,2*inner]; mq, mv float32 [N,M,inner] -> feat_out [N,D,H,W,inner], map_out [N,M,inner], colstat."""
-    _dev_ok(qv, mq, mv)
+    _view_ok(qv)
+    _dev_ok(mq, mv)
     N, Lr, inner = int(qv.shape[0]), _spatial(qv), int(qv.shape[-1]) // 2
     M, dh = int(mq.shape[1]), inner // heads
     fo = torch.empty(tuple(qv.shape[:-1]) + (inner,), dtype=qv.dtype, device=qv.device)
@@ -1069,7 +1127,8 @@ def bidir_attn_fwd(qv, mq, mv, heads: int, scale: float):
 
 
 def bidir_attn_bwd(qv, mq, mv, cs, mo, dfo, dmo, heads: int, scale: float):
-    _dev_ok(qv, mq, mv, cs, mo, dfo, dmo)
+    _view_ok(qv)
+    _dev_ok(mq, mv, cs, mo, dfo, dmo)
     N, Lr, inner = int(qv.shape[0]), _spatial(qv), int(qv.shape[-1]) // 2
     M, dh = int(mq.shape[1]), inner // heads
     dqv = torch.empty(tuple(qv.shape), dtype=qv.dtype, device=qv.device)
@@ -1326,7 +1385,7 @@ def bidir_attn_gemm_bwd(qv, mq, mv, P, Cs, mo, dfo, dmo, heads: int, scale: floa
 
 def colsoftmax_pool_fwd(fw, Cf: int):
     """fw [N,D,H,W,Cf+M] -> map float32 [N,Cf,M], colstat float32 [N,M,2]."""
-    _dev_ok(fw)
+    _view_ok(fw)
     N, Lr, M = int(fw.shape[0]), _spatial(fw), int(fw.shape[-1]) - Cf
     L = _lib.lib()
     nbytes = L.cbim_colsoftmax_pool_workspace(N, Lr, Cf, M)
@@ -1343,7 +1402,8 @@ MAPPOOL_BWD_GEMM_MAX_L = 1024   # voxels per image up to which it is used
 
 
 def colsoftmax_pool_bwd(fw, Cf: int, mp, cs, dmap):
-    _dev_ok(fw, mp, cs, dmap)
+    _view_ok(fw)
+    _dev_ok(mp, cs, dmap)
     N, Lr, M = int(fw.shape[0]), _spatial(fw), int(fw.shape[-1]) - Cf
     if MAPPOOL_BWD_GEMM and Lr <= MAPPOOL_BWD_GEMM_MAX_L:
         # the backward of map[c][j] = sum_l f[l][c] P[l][j], P = softmax over the voxels l of the logits z, is GEMM shaped:
@@ -1549,7 +1609,8 @@ def token_linear_wgrad(x2d, dy2d, act_in: int = 0, out=None):
 
 def as_rows(t):
     """a gradient as the kernels can read it: the tensor itself when it is contiguous or a channel-slice view of a wider
-    channels-last tensor (row stride > channel count: what torch.cat's backward hands out — no copy), else a contiguous copy"""
+    channels-last tensor that _view_ok admits (row stride > channel count: what torch.cat's backward hands out — no copy), else a
+    contiguous copy"""
     return t if (t.is_contiguous() or _is_row_view(t)) else t.contiguous()
 
 
@@ -1567,7 +1628,8 @@ def colsum(x2d):
 
 def resnorm_fwd(a, stats_a, b, stats_b, act: int):
     """y = act(IN(a) + (IN(b) if stats_b is given else b))."""
-    _dev_ok(a, stats_a, b, stats_b)
+    _view_ok(a, b)
+    _dev_ok(stats_a, stats_b)
     N, Cc, S = int(a.shape[0]), int(a.shape[-1]), _spatial(a)
     y = torch.empty(tuple(a.shape), dtype=a.dtype, device=a.device)
     check(_lib.lib().cbim_resnorm_fwd(_dt(a), _p(a), _rs(a), _p(stats_a), _p(b), _rs(b), _p(stats_b), _p(y), Cc, N, S, Cc, act,
@@ -1576,7 +1638,8 @@ def resnorm_fwd(a, stats_a, b, stats_b, act: int):
 
 
 def resnorm_bwd(dy, a, stats_a, b, stats_b, act: int, need_db: bool = True):
-    _dev_ok(dy, a, stats_a, b, stats_b)
+    _view_ok(dy, a, b)
+    _dev_ok(stats_a, stats_b)
     N, Cc, S = int(a.shape[0]), int(a.shape[-1]), _spatial(a)
     L = _lib.lib()
     P = L.cbim_stats_parts(S, Cc)
