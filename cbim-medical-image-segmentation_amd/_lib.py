@@ -135,6 +135,10 @@ _SIGS = {
     "cbim_topk_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, vp, vp]),
     "cbim_affine_sample3d": (i32, [vp, vp, i32, vp, vp, vp] + [i32] * 10 + [vp]),
     "cbim_crop3d": (i32, [vp, vp, i32, vp, vp] + [i32] * 10 + [vp]),
+    "cbim_class_index_chunk": (i32, []),
+    "cbim_class_index": (i32, [vp, i32, i64, i32, vp, vp, vp]),
+    "cbim_pick_voxel": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, C.c_uint64, f64, f64, vp, vp]),
+    "cbim_crop3d_at": (i32, [vp, vp, i32, vp, vp] + [i32] * 7 + [vp] + [i32] * 6 + [vp]),
     "cbim_chan_stats_workspace": (sz, [i32, i64]),
     "cbim_chan_stats": (i32, [vp, i32, i64, vp, vp, sz, vp]),
     "cbim_intensity": (i32, [vp, vp, i32, i64, i32, vp, i32, vp, vp, i32, vp, vp]),

@@ -111,6 +111,20 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #endif
 }
+// ordered counting inside one wave (the ballot itself: wave_ballot of atomics_compat.h).  ballot_rank: how many lanes BELOW
+// `lane` have their bit set — with the ballot of a predicate, the lane's rank among the lanes where it holds, in lane order.
+__device__ __forceinline__ int ballot_rank(unsigned long long ballot, int lane) {
+  return __builtin_popcountll(ballot & ((1ull << lane) - 1ull));
+}
+// inclusive prefix sum over the 64 lanes, in lane order (six ds_bpermute steps: for latency-bound selects, not for hot loops)
+__device__ __forceinline__ long long wave_scan_incl(long long v, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const long long o = __shfl(v, (lane - d) & 63, 64);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
 // 4 consecutive-voxel bf16 of one channel via the LDS transpose read ds_read_b64_tr_b16 (per-lane address of 4 bf16)
 __device__ __forceinline__ u32x2 lds_tr16_b64(const unsigned char* p) {
 #ifdef CBIM_EMU

@@ -559,6 +559,7 @@ extern "C" int cbim_warm_predict(void* stream);
 extern "C" int cbim_warm_components(void* stream);
 extern "C" int cbim_warm_focal(void* stream);
 extern "C" int cbim_warm_topk(void* stream);
+extern "C" int cbim_warm_sample(void* stream);
 
 // One successful no-op launch from every code object of the library (see CBIM_DEFINE_WARM); the binding calls
 // this once per process before the first real launch.
@@ -590,6 +591,7 @@ extern "C" int cbim_runtime_warmup(void* stream) {
   if (int e = cbim_warm_components(stream)) return e;
   if (int e = cbim_warm_focal(stream)) return e;
   if (int e = cbim_warm_topk(stream)) return e;
+  if (int e = cbim_warm_sample(stream)) return e;
   return CBIM_OK;
 }
 

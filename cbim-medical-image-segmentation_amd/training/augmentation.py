@@ -275,3 +275,110 @@ def crop_around_coordinate_3d(tensor_img, tensor_lab, crop_size, coordinate, mod
     else:
         org = [min(max(0, c - math.ceil(s / 2)), d - s) for c, s, d in zip((z, y, x), cs, dims)]
     return _crop_at(tensor_img, tensor_lab, list(cs), *org)
+
+
+# ---- foreground-oversampled sampling on the device (csrc/sample_kernels.hip) -----------------------------------------------
+
+class ClassIndex:
+    """Per-volume class index: ``totals`` int64 [K+1] (totals[K] = labels outside [0, K)), ``table`` int32 [K, nchunk]
+    (voxels of class c in chunk j of cbim_class_index_chunk() consecutive voxels), the volume's ``shape`` (D, H, W),
+    ``K`` and ``lab``, the contiguous label tensor it was built from (pick_class_voxel reads one chunk of it)."""
+
+    def __init__(self, lab, num_classes, totals, table):
+        self.lab, self.K, self.totals, self.table = lab, int(num_classes), totals, table
+        self.shape = tuple(int(v) for v in lab.shape[-3:])
+
+    def counts(self):
+        """voxels per class, int64 [K], on the host (one synchronisation)"""
+        return self.totals[:self.K].cpu()
+
+    def ignored(self):
+        """number of labels outside [0, K) (one synchronisation)"""
+        return int(self.totals[self.K])
+
+    def _check(self):
+        D, H, W = self.shape
+        nchunk = -(-(D * H * W) // _lib.lib().cbim_class_index_chunk())
+        if (self.lab.numel() != D * H * W or not self.lab.is_contiguous() or tuple(self.table.shape) != (self.K, nchunk)
+                or self.totals.numel() != self.K + 1 or self.table.dtype != torch.int32
+                or self.totals.dtype != torch.int64 or not self.table.is_contiguous() or not self.totals.is_contiguous()):
+            raise ValueError(f"cbim_amd: class index (K={self.K}, table {tuple(self.table.shape)}) was not built for a "
+                             f"label volume of shape {tuple(self.lab.shape)}")
+        _dev_ok(self.lab, self.totals, self.table)
+
+
+def class_index(tensor_lab, num_classes):
+    """Build the class index of one label volume ([D,H,W], or with leading dimensions of 1; int8 or int64) in one read of
+    it, on the current stream.  2 <= num_classes <= 64."""
+    K = int(num_classes)
+    if not 2 <= K <= 64:
+        raise ValueError(f"cbim_amd: class_index needs 2 <= num_classes <= 64, got {num_classes}")
+    if tensor_lab.dim() < 3 or any(int(v) != 1 for v in tensor_lab.shape[:-3]) or tensor_lab.numel() == 0:
+        raise ValueError(f"cbim_amd: class_index takes one [D,H,W] label volume, got shape {tuple(tensor_lab.shape)}")
+    lab = tensor_lab.contiguous()
+    _dev_ok(lab)
+    L = _lib.lib()
+    S = lab.numel()
+    nchunk = -(-S // L.cbim_class_index_chunk())
+    totals = torch.empty((K + 1,), dtype=torch.int64, device=lab.device)
+    table = torch.empty((K, nchunk), dtype=torch.int32, device=lab.device)
+    check(L.cbim_class_index(_p(lab), _lab_bytes(lab), S, K, _p(totals), _p(table), _stream(lab)), "class_index")
+    return ClassIndex(lab, K, totals, table)
+
+
+def pick_class_voxel(index, u_class, u_rank, classes=None):
+    """int32 [4] DEVICE tensor {z, y, x, c}: a uniformly random voxel of a uniformly random class among ``classes``
+    (default: the foreground classes 1 .. K-1) that the volume contains; {-1, -1, -1, -1} if it contains none of them.
+    With n such classes in ascending order the class is number min(int(u_class * n), n - 1) and the voxel is number
+    min(int(u_rank * count), count - 1) of that class in row-major order (np.argwhere order).  One launch, no
+    synchronisation.  u_class and u_rank (host floats in [0, 1)) are passed to the kernel BY VALUE: a captured graph
+    replays the draw it was captured with."""
+    index._check()
+    K = index.K
+    cls = range(1, K) if classes is None else [int(c) for c in classes]
+    mask = 0
+    for c in cls:
+        if not 0 <= c < K:
+            raise ValueError(f"cbim_amd: class {c} outside [0, {K})")
+        mask |= 1 << c
+    u_class, u_rank = float(u_class), float(u_rank)
+    if not (0.0 <= u_class < 1.0 and 0.0 <= u_rank < 1.0):
+        raise ValueError(f"cbim_amd: the draws ({u_class}, {u_rank}) must lie in [0, 1)")
+    D, H, W = index.shape
+    out = torch.empty((4,), dtype=torch.int32, device=index.lab.device)
+    check(_lib.lib().cbim_pick_voxel(_p(index.lab), _lab_bytes(index.lab), D, H, W, K, _p(index.totals), _p(index.table),
+                                     mask, u_class, u_rank, _p(out), _stream(index.lab)), "pick_voxel")
+    return out
+
+
+def crop_around_device_coordinate_3d(tensor_img, tensor_lab, crop_size, coord, jitter=None, fallback=(0, 0, 0)):
+    """crop_around_coordinate_3d with the coordinate in device memory (``coord``: int32 [4] as pick_class_voxel returns
+    it; only z, y, x are read): the window origin per axis is min(max(0, coord_a - jitter_a), dim_a - size_a), computed in
+    the kernel.  jitter=None is the reference's centre rule, ceil(size_a / 2) (mode="center", augmentation.py:346-382);
+    any 0 <= jitter_a < size_a puts the voxel at that offset inside the window, border clamping aside.  coord[0] < 0
+    (nothing to pick) gives the window at ``fallback``.  No synchronisation."""
+    if isinstance(crop_size, int):
+        crop_size = [crop_size] * 3
+    _need5(tensor_img)
+    _dev_ok(tensor_img, tensor_lab, coord)
+    cs = [int(c) for c in crop_size]
+    _, Cc, D, H, W = tensor_img.shape
+    if any(s < 1 or s > d for s, d in zip(cs, (D, H, W))):
+        raise ValueError(f"cbim_amd: crop {tuple(cs)} does not fit the {(D, H, W)} volume")
+    if coord.dtype != torch.int32 or coord.numel() < 3 or not coord.is_contiguous():
+        raise ValueError("cbim_amd: coord must be a contiguous int32 device tensor {z, y, x[, class]}")
+    if jitter is None:
+        jit = [math.ceil(s / 2) for s in cs]
+    else:
+        jit = [int(j) for j in jitter]
+        if any(not 0 <= j < s for j, s in zip(jit, cs)):
+            raise ValueError(f"cbim_amd: jitter {tuple(jit)} outside [0, crop size)")
+    fb = [int(f) for f in fallback]
+    if any(f < 0 or f + s > d for f, s, d in zip(fb, cs, (D, H, W))):
+        raise ValueError(f"cbim_amd: fallback window {tuple(fb)}+{tuple(cs)} leaves the {(D, H, W)} volume")
+    img, lab = tensor_img.contiguous(), tensor_lab.contiguous()
+    oimg = torch.empty((1, Cc) + tuple(cs), dtype=torch.float32, device=img.device)
+    olab = torch.empty((1, 1) + tuple(cs), dtype=lab.dtype, device=img.device)
+    check(_lib.lib().cbim_crop3d_at(_p(img), _p(lab), _lab_bytes(lab), _p(oimg), _p(olab), Cc, D, H, W, *cs, _p(coord),
+                                    *jit, *fb, _stream(img)), "crop3d_at")
+    return oimg, olab

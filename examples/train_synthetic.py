@@ -35,7 +35,7 @@ def synthetic_volume(classes, size, gen, device):
 
 
 def run(config="amos_ct/resunet_3d.yaml", iters=20, epochs=2, base=None, size=None, device=None, dtype="bf16", seed=2023,
-        n_volumes=3, verbose=True, sliding_window=True):
+        n_volumes=3, verbose=True, sliding_window=True, oversample_foreground=0.0):
     import cbim_amd
     from cbim_amd.inference.utils import get_inference
     from cbim_amd.metric.utils import calculate_dice
@@ -54,7 +54,8 @@ def run(config="amos_ct/resunet_3d.yaml", iters=20, epochs=2, base=None, size=No
     # the optimisation keys every shipped 3D yaml carries (e.g. config/amos_ct/resunet_3d.yaml:26-47)
     cfg.update(optimizer="adamw", base_lr=6e-4, betas=[0.9, 0.999], weight_decay=0.05, ema_alpha=0.99, epochs=epochs,
                affine_pad_size=[max(s // 4, 2) for s in cfg["training_size"]], scale=[0.3] * 3, rotate=[30] * 3,
-               translate=[0] * 3, sliding_window=sliding_window)
+               translate=[0] * 3, sliding_window=sliding_window, oversample_foreground=oversample_foreground,
+               num_classes=cfg["classes"])
     args = argparse.Namespace(**cfg)
     device = device or torch.device("cuda", 0)
     cbim_amd.set_compute_dtype(dtype)
@@ -115,5 +116,6 @@ if __name__ == "__main__":
     ap.add_argument("--base", type=int, default=None)
     ap.add_argument("--size", type=int, nargs=3, default=None)
     ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--oversample-foreground", type=float, default=0.0)
     a = ap.parse_args()
-    run(a.config, a.iters, a.epochs, a.base, a.size, dtype=a.dtype)
+    run(a.config, a.iters, a.epochs, a.base, a.size, dtype=a.dtype, oversample_foreground=a.oversample_foreground)

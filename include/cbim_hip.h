@@ -416,6 +416,32 @@ int cbim_affine_sample3d(const float* img, const void* lab, int lab_bytes, const
 /* crop_3d (augmentation.py:320-343) of image and label (label keeps its dtype). */
 int cbim_crop3d(const float* img, const void* lab, int lab_bytes, float* out_img, void* out_lab, int C,
                 int Di, int Hi, int Wi, int Do, int Ho, int Wo, int d0, int h0, int w0, void* stream);
+/* Foreground-oversampled patch sampling (nnU-Net's rule; the reference's datasets only crop uniformly) for label volumes
+ * that stay on the device: an index built once per volume, then per forced sample "the r-th voxel of class c" and a crop
+ * around it, with no host round trip (csrc/sample_kernels.hip).  lab: [D][H][W] int8 (lab_bytes 1) or int64 (8), S = D*H*W.
+ *   cbim_class_index_chunk : voxels per index chunk (a compile-time constant, at most 8192); nchunk = ceil(S / chunk).
+ *   cbim_class_index : one read of the volume.  table int32 [K][nchunk]: table[c][j] = voxels equal to c among voxels
+ *       j*chunk .. min(S, (j+1)*chunk) - 1 in row-major order; totals int64 [K+1]: totals[c] = voxels of class c,
+ *       totals[K] = labels outside [0, K) (they belong to no class and are never indexed with).  2 <= K <= 64.
+ *       Integer atomics only: bitwise reproducible.
+ *   cbim_pick_voxel : ONE launch of one workgroup.  The eligible classes are those with bit c of class_mask set and
+ *       totals[c] > 0, in ascending order, n of them.  n == 0: out = {-1,-1,-1,-1}.  Otherwise c = the class at position
+ *       min((int64)(u_class * (double)n), n - 1) of that list, r = min((int64)(u_rank * (double)totals[c]), totals[c] - 1)
+ *       (both products in IEEE double, as written), out int32 [4] = {z, y, x, c} of the r-th voxel of class c in row-major
+ *       order.  u_class, u_rank in [0, 1) are BY-VALUE arguments like theta12 above: a captured graph replays the draw it
+ *       was captured with.  Reads K totals, nchunk int32 of the table and one chunk of labels.  If lab is not the volume the
+ *       index was built from, the pick is some voxel of lab or {-1,-1,-1,-1}, never an access outside lab.
+ *   cbim_crop3d_at : cbim_crop3d with the origin computed in the kernel from coord (DEVICE int32 [4], e.g. the pick):
+ *       coord[0] >= 0: origin_a = min(max(0, coord_a - j_a), dim_a - size_a) (j_a = ceil(size_a / 2) is
+ *       crop_around_coordinate_3d(mode="center"), augmentation.py:346-382; any 0 <= j_a < size_a keeps the voxel inside the
+ *       window); coord[0] < 0 (nothing to pick): the fallback origin (fz, fy, fx).  size_a > dim_a is refused. */
+int cbim_class_index_chunk(void);
+int cbim_class_index(const void* lab, int lab_bytes, int64_t S, int K, int64_t* totals, int32_t* table, void* stream);
+int cbim_pick_voxel(const void* lab, int lab_bytes, int D, int H, int W, int K, const int64_t* totals,
+                    const int32_t* table, uint64_t class_mask, double u_class, double u_rank, int32_t* out, void* stream);
+int cbim_crop3d_at(const float* img, const void* lab, int lab_bytes, float* out_img, void* out_lab, int C, int Di, int Hi,
+                   int Wi, int Do, int Ho, int Wo, const int32_t* coord, int jz, int jy, int jx, int fz, int fy, int fx,
+                   void* stream);
 /* per-channel (min, max, mean, unbiased std): float [C][4]  (gamma :117-124, contrast :150-155). */
 size_t cbim_chan_stats_workspace(int C, int64_t S);
 int cbim_chan_stats(const float* x, int C, int64_t S, float* stats, void* workspace, size_t ws_bytes,
